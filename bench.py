@@ -18,6 +18,12 @@ untimed sweep per copy) before the timed region starts, whatever --warmup is.
 N > 1 (one process per GPU, launched by torch.distributed.run): every rank sweeps its own copies (fixed work per GPU,
 no data-path collective; weak scaling); value = bytes swept by all ranks / max-over-ranks time.  The row-panel-sharded
 SpGEMM with its RCCL allgatherv (configs[4]) is timed in the same run and reported under `spgemm_sharded`.
+
+A plain run does only what the headline needs: set-up, --warmup sweeps, the --steps timed sweeps, the result line.  Everything
+else -- the cache-warm figure, `spmv_structures`, `spgemm`, the sharded operators, the rocSPARSE `vendor` column and the
+`cpu_baseline` -- runs with --full (the --skip-* switches then leave parts out).  --dump-outputs DIR writes what the last timed
+sweep returned, y = A*x, as DIR/y.npy (float32; a fixed seeded sample when it exceeds 64 MB); the inputs are seeded, so two builds
+can be compared output for output.
 """
 import argparse
 import glob
@@ -39,6 +45,8 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="also the cache-warm figure, SpMV structures, SpGEMM, sharded operators, vendor column and CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--mtx-dir", default=os.environ.get("BMSP_MTX_DIR", ""))
     ap.add_argument("--scale", type=int, default=20, help="R-MAT scale of the synthetic SpMV workload")
     ap.add_argument("--edge-factor", type=float, default=2.0)
@@ -55,7 +63,10 @@ def parse(argv=None):
     ap.add_argument("--vendor-timeout", type=float, default=150.0, help="the rocSPARSE column runs in a child process; on a fresh box paging librocsparse in can take minutes")
     ap.add_argument("--vendor-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the child launcher started by --gpus N > 1 (0: a free one)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launcher_command(gpus, argv, port):
@@ -246,6 +257,23 @@ def note(msg):
     print("[bench %6.1f s] %s" % (time.time() - _T0, msg), file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, np):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64).  An array above its share of 64 MB is cut to a sample whose
+    indices come from a fixed seed, so that two runs with the same arguments write the same elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    note("outputs written to %s: %s" % (path, ", ".join(sorted(arrays))))
+
+
 def vendor_in_child(args):
     """the rocSPARSE column in a child process with a deadline, so that a cold librocsparse (GBs of code objects to page in on a fresh
     box) can never take the bench line down or past its time budget"""
@@ -367,10 +395,8 @@ def main():
         wall = float(t.item())
     ms_per_step = wall * 1e3 / args.steps
     value = world * eff_bytes * args.steps / wall / 1e9  # every rank sweeps the same amount of its own data
-
-    # cache-warm sweep (one copy only), for information
-    S.timed(10, variant, rotate=False)
-    warm_ms = S.timed(args.steps, variant, rotate=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": S.ys[(args.steps - 1) % copies].to_host()}, np)  # y of the last timed sweep
 
     kern_ms = dev_ms / args.steps  # HIP events on the launch stream, over the timed region
     # what was launched and what that launch must move: asked from the library (bmsp_spmv_launch_info mirrors the launcher's decisions and
@@ -398,54 +424,60 @@ def main():
                       "blocks": info["block_num"], "values_per_tile": round(info["nnz"] / max(1, info["block_num"]), 3),
                       "x": "ones", "variant": ["default (value-stream sweep over the cached plan)", "batched", "row-group"][variant],
                       "hbm_resident_copies_rotated": copies, "effective_bytes_per_spmv": eff_bytes},
-           "warm_ms_per_step": round(warm_ms, 5), "warm_effective_GBs": round(eff_bytes / (warm_ms * 1e-3) / 1e9, 1),
            "prepare_ms": round(S.prepare_ms, 4), "prepare_warm_ms": round(S.prepare_warm_ms, 4),
            "prepare_note": "sweep plan + position cache of one matrix (bmsp_matrix_prepare, host wall time incl. its read-backs): outside the timed region, paid once per matrix; prepare_warm_ms = the same for the second matrix of the process (kernels loaded, pool warm)",
            "roofline": roofline}
 
     note("SpMV headline timed")
-    # ---------------- the same sweep on denser structures (driver-verifiable roofline fractions) ----------------
-    if not args.skip_structures and not use_dist and not args.spmv_matrix:
-        out["spmv_structures"] = bench_spmv_structures(B, gen, np, S)
-    mats0, x0, y0 = S.mats[0], S.x, S.ys[0]
-    if not use_dist:
-        del S.mats[1:], S.ys[1:]
+    # ---------------- --full: everything below is beside the headline; a plain run prints the line now ----------------
+    if args.full:
+        # cache-warm sweep (one copy only), for information
+        S.timed(10, variant, rotate=False)
+        warm_ms = S.timed(args.steps, variant, rotate=False)
+        out["warm_ms_per_step"] = round(warm_ms, 5)
+        out["warm_effective_GBs"] = round(eff_bytes / (warm_ms * 1e-3) / 1e9, 1)
+        # ---------------- the same sweep on denser structures (driver-verifiable roofline fractions) ----------------
+        if not args.skip_structures and not use_dist and not args.spmv_matrix:
+            out["spmv_structures"] = bench_spmv_structures(B, gen, np, S)
+        mats0, x0, y0 = S.mats[0], S.x, S.ys[0]
+        if not use_dist:
+            del S.mats[1:], S.ys[1:]
 
-    note("SpMV structures done")
-    # ---------------- SpGEMM (configs[2], configs[3], dense-tile ceiling) on rank 0 / single GPU ----------------
-    if not args.skip_spgemm and not use_dist:
-        out["spgemm"] = bench_spgemm(B, gen, np, args)
-    # the sharded operators are extras next to the headline line: a failure in them (RCCL rendezvous, memory) must not lose the line
-    if use_dist and not args.skip_spgemm:
-        try:
-            out["spgemm_sharded"] = bench_spgemm_sharded(B, gen, np, torch, dist, rank, world)
-            # top-level, where a parser of the line looks: aggregate SpGEMM rate of the sharded product, its single-GPU value measured in
-            # this same run, and their ratio (the headline `value` above is a no-communication replica rate and scales by construction)
-            sg = out["spgemm_sharded"]
-            out["spgemm_sharded_gflops"] = sg.get("gflops")
-            out["spgemm_single_gpu_gflops"] = sg.get("single_gpu_gflops")
-            out["spgemm_sharded_speedup"] = sg.get("speedup_vs_single_gpu")
-            out["spgemm_owner_keeps_gflops"] = sg.get("owner_keeps", {}).get("gflops")
-            out["spgemm_owner_keeps_speedup"] = sg.get("owner_keeps", {}).get("speedup_vs_single_gpu")
-            out["spgemm_exchange_hidden_frac"] = sg.get("exchange_hidden_frac")
-        except Exception as e:  # noqa: BLE001
-            out["spgemm_sharded"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if use_dist:
-        try:
-            out["spmv_sharded"] = bench_spmv_sharded(B, np, torch, dist, rank, world, mats0, x0, y0)
-        except Exception as e:  # noqa: BLE001
-            out["spmv_sharded"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        note("SpMV structures done")
+        # ---------------- SpGEMM (configs[2], configs[3], dense-tile ceiling) on rank 0 / single GPU ----------------
+        if not args.skip_spgemm and not use_dist:
+            out["spgemm"] = bench_spgemm(B, gen, np, args)
+        # the sharded operators are extras next to the headline line: a failure in them (RCCL rendezvous, memory) must not lose the line
+        if use_dist and not args.skip_spgemm:
+            try:
+                out["spgemm_sharded"] = bench_spgemm_sharded(B, gen, np, torch, dist, rank, world)
+                # top-level, where a parser of the line looks: aggregate SpGEMM rate of the sharded product, its single-GPU value measured in
+                # this same run, and their ratio (the headline `value` above is a no-communication replica rate and scales by construction)
+                sg = out["spgemm_sharded"]
+                out["spgemm_sharded_gflops"] = sg.get("gflops")
+                out["spgemm_single_gpu_gflops"] = sg.get("single_gpu_gflops")
+                out["spgemm_sharded_speedup"] = sg.get("speedup_vs_single_gpu")
+                out["spgemm_owner_keeps_gflops"] = sg.get("owner_keeps", {}).get("gflops")
+                out["spgemm_owner_keeps_speedup"] = sg.get("owner_keeps", {}).get("speedup_vs_single_gpu")
+                out["spgemm_exchange_hidden_frac"] = sg.get("exchange_hidden_frac")
+            except Exception as e:  # noqa: BLE001
+                out["spgemm_sharded"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        if use_dist:
+            try:
+                out["spmv_sharded"] = bench_spmv_sharded(B, np, torch, dist, rank, world, mats0, x0, y0)
+            except Exception as e:  # noqa: BLE001
+                out["spmv_sharded"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    note("SpGEMM done")
-    # ---------------- vendor comparison column (rocSPARSE CSR on the same matrices; reporting only) ----------------
-    if rank == 0 and not use_dist and not args.skip_vendor:
-        out["vendor"] = vendor_in_child(args)
-    note("vendor column done")
-    # ---------------- CPU baseline (cusp::multiply restatement) on rank 0, N = 1 only ----------------
-    if rank == 0 and not use_dist and not args.skip_cpu:
-        out["cpu_baseline"] = cpu_baseline(wl, eff_bytes, args)
+        note("SpGEMM done")
+        # ---------------- vendor comparison column (rocSPARSE CSR on the same matrices; reporting only) ----------------
+        if rank == 0 and not use_dist and not args.skip_vendor:
+            out["vendor"] = vendor_in_child(args)
+        note("vendor column done")
+        # ---------------- CPU baseline (cusp::multiply restatement) on rank 0, N = 1 only ----------------
+        if rank == 0 and not use_dist and not args.skip_cpu:
+            out["cpu_baseline"] = cpu_baseline(wl, eff_bytes, args)
 
-    note("CPU baseline done")
+        note("CPU baseline done")
     if rank == 0:
         print(json.dumps(out))
     if dist is not None:

@@ -61,3 +61,27 @@ def test_suitesparse_dimensions_are_asserted():
         bench.assert_suitesparse_dims("/data/cage12.mtx", dict(ok, nnz=2032535))
     with pytest.raises(AssertionError):
         bench.assert_suitesparse_dims("/data/webbase-1M.mtx", ok)
+
+
+def test_plain_run_is_the_default():
+    """a plain run times the headline only; the rest of the line needs --full; --steps is the number of timed steps"""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    assert bench.parse(["--full", "--dump-outputs", "out"]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files; an array above the size cap is cut to the same seeded sample every time"""
+    import numpy as np
+    y = np.arange(5000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), {"y": y}, np)
+    np.testing.assert_array_equal(np.load(str(tmp_path / "whole" / "y.npy")), y)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y}, np)
+    a, b = np.load(str(tmp_path / "a" / "y.npy")), np.load(str(tmp_path / "b" / "y.npy"))
+    assert a.dtype == np.float32 and a.nbytes <= 4000 and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "c"), {"k": np.arange(3, dtype=np.int64)}, np)

@@ -11,6 +11,29 @@ import numpy as np
 import pytest
 
 
+def _spawn(fn, nprocs, *args):
+    """fn(rank, *args) in nprocs fresh processes, as torch.multiprocessing.spawn does -- but without importing torch HERE: torch in the
+    pytest process loads its own HIP runtime and librccl beside libbmsp.so's, and the RCCL tests later in the same session would bind to
+    torch's copy"""
+    import multiprocessing
+    from multiprocessing.connection import wait
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(r,) + args) for r in range(nprocs)]
+    for p in procs:
+        p.start()
+    live = list(procs)
+    while live:  # a rank that fails takes the others down (they would wait at the rendezvous), as torch's spawn does
+        wait([p.sentinel for p in live])
+        live = [p for p in live if p.is_alive()]
+        if any(p.exitcode for p in procs if not p.is_alive()):
+            for p in live:
+                p.terminate()
+            break
+    for p in procs:
+        p.join()
+    assert [p.exitcode for p in procs] == [0] * nprocs
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -154,9 +177,8 @@ def _spmv_worker(rank, world, port, out_dir):
 
 def test_sharded_spmv_exchange_world2(tmp_path):
     """SURVEY 8(e), SpMV row: nnz-balanced block-row panels, x replicated, the y slices broadcast in place."""
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_spmv_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_spmv_worker, 2, 2, port, str(tmp_path))
     res = [open(tmp_path / ("spmv_rank%d.txt" % r)).read().split() for r in range(2)]
     assert all(r[0] == "1" for r in res), res
     assert res[0][1] == res[1][1] and int(res[0][1]) > 0
@@ -165,9 +187,8 @@ def test_sharded_spmv_exchange_world2(tmp_path):
 
 
 def test_sharded_spgemm_exchange_world2(tmp_path):
-    import torch.multiprocessing as mp
     port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_worker, 2, 2, port, str(tmp_path))
     res = [open(tmp_path / ("rank%d.txt" % r)).read().split() for r in range(2)]
     assert all(r[0] == "1" for r in res), res            # every rank reassembled exactly the whole product
     assert res[0][1] == res[1][1] and int(res[0][1]) > 0  # same gathered byte count on both ranks

@@ -1,7 +1,7 @@
 #!/bin/bash
 # experiment helper: SpMV bench over several synthetic matrix families (prints one summary line per run)
 for m in "" "--spmv-matrix banded:1048576:8" "--spmv-matrix banded:1048576:8 --batched 1" "--spmv-matrix rmat:20:16" "--spmv-matrix cage:1000000" "$@"; do
-  timeout -k 10 300 python bench.py --skip-spgemm --skip-cpu $m 2>&1 | python -c "
+  timeout -k 10 300 python bench.py --full --skip-spgemm --skip-cpu $m 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     try: d=json.loads(l)

@@ -1,5 +1,6 @@
 import sys, os, time
-sys.path.insert(0, "/root/repo/bmsparse-spgemm-spmv_amd"); sys.path.insert(0, "/root/repo")
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "bmsparse-spgemm-spmv_amd")); sys.path.insert(0, REPO)
 import numpy as np, pybmsp as B
 from pybmsp import gen
 n, _, r, c, v = gen.rmat(20, 2.0)

@@ -4,7 +4,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 python3 $GRAFT_REPO_ROOT/tools/source_hash.py > $OUT/source_hash.json
 cd /tmp && export TMPDIR=/tmp
-ARGS="--skip-cpu --skip-spgemm --skip-vendor --steps 100 --warmup 10 $@"
+ARGS="--full --skip-cpu --skip-spgemm --skip-vendor --steps 100 --warmup 10 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/trace.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS --output-format csv -d $OUT/pmc_sq1 -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/pmc_sq1.log 2>&1
 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/pmc_sq2 -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS > $OUT/pmc_sq2.log 2>&1

@@ -5,7 +5,7 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--skip-cpu --skip-spgemm --skip-vendor --skip-structures --steps 50 --warmup 5 $@"
+ARGS="--full --skip-cpu --skip-spgemm --skip-vendor --skip-structures --steps 50 --warmup 5 $@"
 i=0
 for G in "TA_BUSY_avr TA_TOTAL_WAVEFRONTS_sum" "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum" \
          "TA_BUFFER_READ_WAVEFRONTS_sum TA_FLAT_READ_WAVEFRONTS_sum" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum" \

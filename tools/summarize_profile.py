@@ -13,7 +13,7 @@ def profiled_commit(src):
 
 
 src, tag, kern = sys.argv[1], sys.argv[2], (sys.argv[3] if len(sys.argv) > 3 else "spmv_sweep")
-cmd = sys.argv[4] if len(sys.argv) > 4 else "python3 bench.py --skip-cpu --skip-spgemm --steps 100 --warmup 10"
+cmd = sys.argv[4] if len(sys.argv) > 4 else "python3 bench.py --full --skip-cpu --skip-spgemm --steps 100 --warmup 10"
 os.makedirs("profiles", exist_ok=True)
 stats = sorted(glob.glob(os.path.join(src, "trace/*/*_kernel_stats.csv")), key=os.path.getmtime, reverse=True)
 lines = ["# rocprofv3 summary `%s` (source: %s)" % (tag, src), "",
