@@ -38,6 +38,12 @@ struct bmsp_matrix_s {
     uint16_t *spmv_eoff = nullptr;   // same allocation: per tile, end of its values relative to its item's first value
     int64_t spmv_pos_base = 0, spmv_pos_count = 0;
     int spmv_pos_tried = 0;
+    // chunked sweep (spmv_chunk_kernel): one 32-bit word {row relative to the chunk's first block-row, column} per stored value, padded to
+    // whole chunks | chunk records | arrival counters | carry slots -- one allocation, structure only (kept across value-only invalidation)
+    uint32_t *spmv_cw = nullptr;
+    int64_t spmv_cw_chunks = 0, spmv_cw_split = 0;  // chunks; block-rows folded across chunks
+    size_t spmv_cw_off_rec = 0, spmv_cw_off_cnt = 0, spmv_cw_off_carry = 0;
+    int spmv_cw_colbits = 0, spmv_cw_tried = 0;
     // (bitmap, value offset) of every block as one 16-byte record, for kernels that gather both (block-MAC): built lazily
     uint32_t *block_meta = nullptr;  // block_num x {bmp lo, bmp hi, offset in elements, 0}
     uint32_t *sym_recs = nullptr;    // right operands: block_num x {bitmap ROW-major (lo, hi), block column, rows the tile uses}: all the column-window passes (rowwindow.hip) read per candidate pair

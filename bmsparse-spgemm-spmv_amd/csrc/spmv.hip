@@ -4,7 +4,9 @@
 // block-row, one lane per tile ELEMENT, serial loop over the row's tiles) and spmv_kernel_new (:84-150, the "batched"
 // path: several tiles per step, wide lane reduction).  Both rebuild a block-row pointer on every call (:199-206).
 //
-// MI355X design (variant 0, the default): the block-vector sweep over a cached plan.  Three kernels share the plan; the launcher picks by
+// MI355X design (variant 0, the default): spmv_chunk_kernel for large fp32 matrices of sparse tiles (one wave per 512 stored values over
+// its own structure cache -- see its header below; BMSP_SPMV_NOCHUNK=1 keeps the value-stream kernel); otherwise the block-vector sweep
+// over a cached plan.  Three kernels share the plan; the launcher picks by
 // the matrix: spmv_vstream_kernel (lane per stored value; matrices of sparse tiles -- see its own header below), spmv_rowgroup_kernel
 // (16 lanes per block-row, 16-byte value loads; >= 16 values per tile and no hub block-row), spmv_sweep_kernel (lane per tile, described
 // here; since round 2 only its FULL-tile variant runs by default, BMSP_SPMV_OLD=1 brings the whole kernel back).
@@ -39,6 +41,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <vector>
+#include <type_traits>
 
 namespace bmsp {
 namespace {
@@ -1072,6 +1075,273 @@ __global__ __launch_bounds__(kThreads) void spmv_rowgroup_kernel(const uint32_t 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// chunked sweep (round 5; the default for the value-stream matrices that fit its encoding, fp32)
+// ---------------------------------------------------------------------------------------------------------
+// The value-stream kernel spends most of a wave's life waiting on a chain of dependent round trips (item -> slot words / entries / values ->
+// LDS slot table -> x gather).  Here the work is cut by STORED VALUES instead: chunk c is values [c*V, (c+1)*V) in storage order, cut
+// anywhere (inside a tile, inside a block-row), one wave per chunk.  A per-matrix structure cache holds ONE 32-bit word per stored value,
+// {row relative to the chunk's first block-row (high bits), column (low `colbits` bits)}, so that everything a wave loads first depends on
+// blockIdx alone: its 32-byte record (scalar), its V words and its V values (lane l: values 8l .. 8l+7 of the chunk, two 16-byte loads of
+// each).  The x gathers follow back to back -- one round trip, then the gathers, then the reduction:
+//   * a chunk inside ONE block-row (hub block-rows: most of a graph's values) keeps eight register sums per lane, reduced by a halving
+//     exchange (10 shuffles) into the eight row sums;
+//   * any other chunk adds runs of equal rows in registers (a lane's eight values are consecutive) and then one ds_add_f32 per run into an
+//     LDS window over the chunk's block-rows (kChWin rows at most).
+// Every row is written once.  Chunk c owns the block-rows from its first one (exclusive when that block-row began in an earlier chunk) up to
+// chunk c+1's first block-row -- empty block-rows included, written as zeros.  A block-row whose values lie in several chunks (ca .. cb) is
+// folded through carry slots: chunk ca parks its 8 partial sums in its TAIL slot, chunks ca+1 .. cb in their HEAD slots; write-through (sc1)
+// stores, drained vmcnt, one agent-scope arrival counter per folded block-row (indexed by ca); the last to arrive sums the slots in chunk
+// order with sc1 loads, writes the 8 rows and resets the counter -- the protocol of the long items above, deterministic, no float atomics.
+#ifndef BMSP_CH_V
+#define BMSP_CH_V 512
+#endif
+constexpr uint32_t kChV = BMSP_CH_V;        // stored values per chunk
+constexpr int kChPer = (int)kChV / 64;      // ... per lane (consecutive)
+static_assert(kChPer % 4 == 0, "a lane loads its values four at a time");
+constexpr uint32_t kChWin = 1024;           // LDS row window of a chunk (4 KB): chunks whose block-rows span more rows take the old kernel
+constexpr int64_t kChMinChunks = 128;       // fewer chunks than this: the value-stream kernel (a bound set by a pinned test, not by the timings)
+enum { kChHead = 1, kChTail = 2 };
+
+struct ChunkRec {             // 32 bytes, one scalar load
+    uint32_t fb;              // block-row of the chunk's first value (base of the relative rows)
+    uint32_t own_b, own_e;    // block-rows [own_b, own_e) are written by this chunk alone
+    uint32_t flags;           // kChHead: block-row fb continues from earlier chunks; kChTail: the last block-row continues into later ones
+    uint32_t head_ca, head_cb;  // chunks of the head block-row
+    uint32_t tail_cb;           // last chunk of the tail block-row (its first is this chunk)
+    uint32_t nwin;              // rows of the window: 8 x (block-rows from the first to the last value)
+};
+
+// the halving exchange: lane l ends with the wave sum of s[k], k = 4*bit5 + 2*bit4 + bit3 of l
+__device__ __forceinline__ float chunk_sum8(const float (&s)[8], int lane)
+{
+    const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8;
+    float t[4], u[2];
+#pragma unroll
+    for (int i = 0; i < 4; i++) t[i] = (h5 ? s[i + 4] : s[i]) + __shfl_xor(h5 ? s[i] : s[i + 4], 32, kWave);
+#pragma unroll
+    for (int i = 0; i < 2; i++) u[i] = (h4 ? t[i + 2] : t[i]) + __shfl_xor(h4 ? t[i] : t[i + 2], 16, kWave);
+    float v = (h3 ? u[1] : u[0]) + __shfl_xor(h3 ? u[0] : u[1], 8, kWave);
+    v += __shfl_xor(v, 4, kWave);
+    v += __shfl_xor(v, 2, kWave);
+    v += __shfl_xor(v, 1, kWave);
+    return v;
+}
+
+// the last of chunks ca .. cb to arrive: slot (ca, tail) + slots (ca+1 .. cb, head), in chunk order
+__device__ __forceinline__ void chunk_fold(const float *__restrict__ carry, float *__restrict__ y, uint32_t *__restrict__ counters, uint32_t ca,
+                                           uint32_t cb, uint32_t br, uint32_t num_rows, int lane)
+{
+    const int r = lane & 7, g = lane >> 3;
+    float sum = 0.f;
+    for (uint32_t k = ca + (uint32_t)g; k <= cb; k += 8)
+        sum += __hip_atomic_load(&carry[((size_t)k * 2 + (k == ca ? 1 : 0)) * 8 + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int d = 8; d < 64; d <<= 1) sum += __shfl_xor(sum, d, kWave);
+    const uint32_t row = br * 8u + (uint32_t)r;
+    if (g == 0 && row < num_rows) y[row] = sum;
+    if (lane == 0) __hip_atomic_store(&counters[ca], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__restrict__ recs, const uint32_t *__restrict__ words,
+                                                            const float *__restrict__ values, const float *__restrict__ x, float *__restrict__ y,
+                                                            float *__restrict__ carry, uint32_t *__restrict__ counters, uint32_t nnz,
+                                                            uint32_t num_rows, uint32_t num_cols, uint32_t colbits)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    __shared__ float win[kChWin];
+    const int lane = lane_id();
+    const uint32_t c = blockIdx.x;
+    const ChunkRec rc = recs[c];
+    const uint32_t first = c * kChV + (uint32_t)(kChPer * lane);
+    const rsrc_t rw = make_rsrc(words, nnz * 4u), rv = make_rsrc(values, nnz * 4u), rx = make_rsrc(x, num_cols * 4u);
+    uint32_t w[kChPer];
+    float a[kChPer], xv[kChPer];
+    if (c * kChV + kChV <= nnz) {  // a whole chunk: 16-byte loads
+#pragma unroll
+        for (int q = 0; q < kChPer; q += 4) {
+            const u4 wq = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rw, (first + q) * 4u, 0, 0));
+            const f4 aq = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (first + q) * 4u, 0, 0));
+#pragma unroll
+            for (int i = 0; i < 4; i++) { w[q + i] = wq[i]; a[q + i] = aq[i]; }
+        }
+    } else {  // the last chunk: element loads, values past nnz read 0
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) {
+            const uint32_t off = first + j < nnz ? (first + j) * 4u : kOob;
+            w[j] = __builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0);
+            a[j] = Buf<float>::ld(rv, off);
+        }
+    }
+    const uint32_t cmask = (1u << colbits) - 1u;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) xv[j] = Buf<float>::ld(rx, first + j < nnz ? (w[j] & cmask) * 4u : kOob);
+
+    if (rc.nwin == 8) {
+        // one block-row: eight register sums per lane
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) {
+            const uint32_t rr = w[j] >> colbits;
+            const float p = first + j < nnz ? a[j] * xv[j] : 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; k++) s[k] += rr == (uint32_t)k ? p : 0.f;
+        }
+        const float v = chunk_sum8(s, lane);
+        if ((lane & 7) == 0) win[((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1)] = v;
+    } else {
+        for (uint32_t e = (uint32_t)lane; e < rc.nwin; e += 64) win[e] = 0.f;
+        __builtin_amdgcn_wave_barrier();
+        // runs of equal rows in registers, one LDS add per run
+        // (the values a lane holds past nnz -- last chunk only -- follow its valid ones: the last valid value ends a run)
+        float run = 0.f;
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) {
+            const uint32_t rr = w[j] >> colbits;
+            const bool on = first + j < nnz;
+            const bool flush = j == kChPer - 1 || first + j + 1 >= nnz || (w[j + (j < kChPer - 1 ? 1 : 0)] >> colbits) != rr;
+            run += on ? a[j] * xv[j] : 0.f;
+            if (flush) {
+                if (on) lds_add(win + rr, run);
+                run = 0.f;
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // the block-rows this chunk owns (rows before the first value -- chunk 0 -- and after the last are zeros)
+    const int32_t base = (int32_t)(rc.fb * 8u);
+    const uint32_t row_end = min(rc.own_e * 8u, num_rows);
+    for (uint32_t row = rc.own_b * 8u + (uint32_t)lane; row < row_end; row += 64) {
+        const int32_t rel = (int32_t)row - base;
+        y[row] = rel >= 0 && rel < (int32_t)rc.nwin ? win[rel] : 0.f;
+    }
+    if (!rc.flags) return;
+    // folded block-rows: park the 8 partial sums, the last arriver folds
+    if ((rc.flags & kChHead) && lane < 8) __hip_atomic_store(&carry[((size_t)c * 2) * 8 + lane], win[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((rc.flags & kChTail) && lane < 8)
+        __hip_atomic_store(&carry[((size_t)c * 2 + 1) * 8 + lane], win[rc.nwin - 8u + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t ticket = 0;
+    if (lane == 0 && (rc.flags & kChHead)) ticket = __hip_atomic_fetch_add(&counters[rc.head_ca], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 1 && (rc.flags & kChTail)) ticket = __hip_atomic_fetch_add(&counters[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t th = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 0), tt = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 1);
+    if ((rc.flags & kChHead) && th == rc.head_cb - rc.head_ca) chunk_fold(carry, y, counters, rc.head_ca, rc.head_cb, rc.fb, num_rows, lane);
+    if ((rc.flags & kChTail) && tt == rc.tail_cb - c) chunk_fold(carry, y, counters, c, rc.tail_cb, rc.fb + rc.nwin / 8u - 1u, num_rows, lane);
+}
+
+// cache build, pass 1: block-row of every chunk's first and last value
+__global__ void chunk_bounds_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ bmps, const uint64_t *__restrict__ offsets,
+                                    uint32_t nb, uint32_t nnz, uint32_t *__restrict__ fbr, uint32_t *__restrict__ lbr)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    const uint32_t o = (uint32_t)offsets[b], n = (uint32_t)__popcll(bmps[b]);
+    if (n == 0) return;
+    const uint32_t br = key_row(keys[b]);
+    for (uint32_t c = (o + kChV - 1) / kChV; c * kChV < o + n; c++) fbr[c] = br;
+    for (uint32_t c = o / kChV; c <= (o + n - 1) / kChV; c++) {
+        const uint32_t e = min((c + 1) * kChV, nnz) - 1u;
+        if (e >= o && e < o + n) lbr[c] = br;
+    }
+}
+
+// pass 2: the value words
+__global__ void chunk_words_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ bmps, const uint64_t *__restrict__ offsets,
+                                   uint32_t nb, const uint32_t *__restrict__ fbr, uint32_t colbits, uint32_t *__restrict__ words)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    uint64_t bm = bmps[b];
+    const uint64_t k = keys[b];
+    const uint32_t br = key_row(k), bc = key_col(k);
+    uint32_t idx = (uint32_t)offsets[b];
+    while (bm) {
+        const uint32_t p = (uint32_t)__clzll((long long)bm);
+        bm &= ~(0x8000000000000000ull >> p);
+        const uint32_t rel = (br - fbr[idx / kChV]) * 8u + (p >> 3);
+        words[idx] = (rel << colbits) | (bc * 8u + (p & 7u));
+        idx++;
+    }
+}
+
+// the chunked sweep's cache: built once per matrix (bmsp_matrix_prepare or the first sweep); nothing is kept for a matrix it does not fit
+void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
+{
+    if (A->spmv_cw || A->spmv_cw_tried) return;
+    A->spmv_cw_tried = 1;
+    if (A->dtype != BMSP_F32 || A->view_values_end || A->view_block_begin || A->nnz == 0 || A->nnz >= (1ll << 30) || A->block_num == 0) return;
+    if ((uintptr_t)A->values & 15u) return;  // 16-byte value loads
+    const uint32_t nnz = (uint32_t)A->nnz, nb = (uint32_t)A->block_num;
+    const uint32_t nch = (nnz + kChV - 1) / kChV;
+    const int colbits = A->num_cols <= 1 ? 1 : 32 - __builtin_clz((uint32_t)A->num_cols - 1u);
+    if (colbits > 28) return;
+    std::vector<uint32_t> fb(nch), lb(nch);
+    {
+        DevBuf<uint32_t> d(2 * (size_t)nch);
+        hipLaunchKernelGGL(chunk_bounds_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, A->keys, A->bmps, A->offsets, nb, nnz, d.p, d.p + nch);
+        BMSP_CHECK_LAUNCH();
+        BMSP_HIP(hipStreamSynchronize(st));
+        copy_d2h_staged(fb.data(), d.p, 4 * (size_t)nch);
+        copy_d2h_staged(lb.data(), d.p + nch, 4 * (size_t)nch);
+    }
+    // records; a chunk whose block-rows do not fit the window (or the row field) sends the whole matrix to the old kernel
+    const uint64_t row_cap = std::min<uint64_t>(kChWin, 1ull << (32 - colbits));
+    std::vector<ChunkRec> rec(nch);
+    const uint32_t nbr = (uint32_t)A->num_block_rows();
+    int64_t split = 0;
+    for (uint32_t c = 0; c < nch; c++) {
+        ChunkRec &r = rec[c];
+        r.fb = fb[c];
+        r.nwin = (lb[c] - fb[c] + 1u) * 8u;
+        if (lb[c] < fb[c] || r.nwin > row_cap) return;
+        const bool head = c > 0 && lb[c - 1] == fb[c], tail = c + 1 < nch && fb[c + 1] == lb[c];
+        r.own_b = c == 0 ? 0u : fb[c] + (head ? 1u : 0u);
+        r.own_e = c + 1 < nch ? fb[c + 1] : nbr;
+        r.flags = (head ? kChHead : 0) | (tail && !(head && fb[c] == lb[c]) ? kChTail : 0);
+        r.head_ca = r.head_cb = r.tail_cb = c;
+    }
+    // chunk ranges of the folded block-rows
+    for (uint32_t c = 0; c < nch; c++) {
+        if (!(rec[c].flags & kChTail)) continue;
+        split++;
+        uint32_t e = c + 1;
+        while (e + 1 < nch && fb[e + 1] == lb[c]) e++;
+        rec[c].tail_cb = e;
+        for (uint32_t k = c + 1; k <= e; k++) { rec[k].head_ca = c; rec[k].head_cb = e; }
+    }
+    // one allocation: words (whole chunks) | records | counters | carry (2 slots x 8 rows per chunk)
+    const size_t off_rec = (size_t)nch * kChV * 4, off_cnt = off_rec + sizeof(ChunkRec) * (size_t)nch;
+    const size_t off_carry = (off_cnt + 4 * (size_t)nch + 63) & ~size_t(63), total = off_carry + 64 * (size_t)nch;
+    char *mem = (char *)pool_alloc(total);
+    BMSP_HIP(hipMemsetAsync(mem, 0, total, st));
+    BMSP_HIP(hipMemcpyAsync(mem + off_rec, rec.data(), sizeof(ChunkRec) * (size_t)nch, hipMemcpyHostToDevice, st));
+    {
+        DevBuf<uint32_t> d(nch);
+        BMSP_HIP(hipMemcpyAsync(d.p, fb.data(), 4 * (size_t)nch, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(chunk_words_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, A->keys, A->bmps, A->offsets, nb, d.p, (uint32_t)colbits, (uint32_t *)mem);
+        BMSP_CHECK_LAUNCH();
+        BMSP_HIP(hipStreamSynchronize(st));  // the host records and the staging buffer go away with this scope
+    }
+    A->spmv_cw = (uint32_t *)mem;
+    A->spmv_cw_chunks = nch;
+    A->spmv_cw_split = split;
+    A->spmv_cw_off_rec = off_rec; A->spmv_cw_off_cnt = off_cnt; A->spmv_cw_off_carry = off_carry;
+    A->spmv_cw_colbits = colbits;
+}
+
+// the chunked sweep takes (A, rows): variant 0, fp32, the whole matrix (no row range, no view), the value-stream kernel not asked for, and
+// (unless BMSP_SPMV_CHUNK=1 asks for it) fewer than 2 values per tile -- the run adds into LDS lose to the value-stream kernel's counting
+// sort on denser tiles (FEM-like 3.7 / tile 42.1 vs 28.6 us, cage-like 3.2 / tile 58.4 vs 56.6) -- and at least kChMinChunks chunks.
+// The cache must also fit (build_chunk_cache).
+bool chunk_wanted(const bmsp_matrix_s *A, uint32_t row_lo, uint32_t row_hi)
+{
+    if (A->dtype != BMSP_F32 || row_lo != 0 || row_hi != (uint32_t)A->num_rows || A->view_values_end || A->view_block_begin) return false;
+    if (getenv("BMSP_SPMV_NOCHUNK") || getenv("BMSP_SPMV_NO_POSCACHE") || getenv("BMSP_SPMV_RED")) return false;
+    if (getenv("BMSP_SPMV_CHUNK")) return true;
+    return A->nnz < 2 * A->block_num && (A->nnz + kChV - 1) / kChV >= kChMinChunks;
+}
+
 template <typename T>
 void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t st, uint32_t row_lo, uint32_t row_hi)
 {
@@ -1110,6 +1380,20 @@ void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t s
         }
         const uint32_t n_items = (uint32_t)A->spmv_num_chunks;
         char *mem = (char *)A->spmv_chunks;
+        if constexpr (std::is_same<T, float>::value) {
+            if (vstream_eligible(A) && chunk_wanted(A, row_lo, row_hi)) {
+                build_chunk_cache(A, st);
+                if (A->spmv_cw) {
+                    const char *cm = (const char *)A->spmv_cw;
+                    hipLaunchKernelGGL(spmv_chunk_kernel, dim3((uint32_t)A->spmv_cw_chunks), dim3(64), 0, st, (const ChunkRec *)(cm + A->spmv_cw_off_rec),
+                                       (const uint32_t *)cm, (const float *)A->values, (const float *)v, (float *)u, (float *)(cm + A->spmv_cw_off_carry),
+                                       (uint32_t *)(cm + A->spmv_cw_off_cnt), (uint32_t)A->nnz, (uint32_t)A->num_rows, (uint32_t)A->num_cols,
+                                       (uint32_t)A->spmv_cw_colbits);
+                    BMSP_CHECK_LAUNCH();
+                    return;
+                }
+            }
+        }
         if (vstream_eligible(A)) {
             build_pos_cache(A, st);
             const bool cached = A->spmv_pos != nullptr;
@@ -1147,6 +1431,8 @@ void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t s
 
 // Which kernel bmsp_spmv launches for (A, variant) -- the launcher's own decisions, in its order -- and the bytes that kernel's layout
 // must move per launch ("compulsory": every array it reads or writes, once; counted from the plan, not estimated):
+//   chunked sweep: value word + value per stored value (8 B) + chunk records (32 B) + x + y + per carry slot its 8 accumulators stored and
+//     read back + per folded block-row its counter (add + reset);
 //   value-stream, position + tile cache: items (32 B) + slot word (4 B per tile) + for items that are NOT a single batch the 2-byte value
 //     end of every tile + entries (2 B) and values per stored value + x + y + carry slots;
 //   value-stream, in-kernel decode: items + keys, bitmaps, offsets (24 B per tile) + values + x + y;
@@ -1174,7 +1460,19 @@ void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kerne
             name = "spmv_rowgroup_kernel";
         } else {
             const int64_t n_items = A->spmv_num_chunks;
-            if (vstream_eligible(A)) {
+            if (vstream_eligible(A) && chunk_wanted(A, 0, (uint32_t)A->num_rows)) build_chunk_cache(A, st);
+            if (vstream_eligible(A) && chunk_wanted(A, 0, (uint32_t)A->num_rows) && A->spmv_cw) {
+                // chunked sweep: value words + values (4 B each per stored value) + records + x + y + the carry slots of the folded
+                // block-rows (8 accumulators stored and read back per chunk that holds a part) and their counters (add + reset)
+                name = "spmv_chunk_kernel";
+                const int64_t nch = A->spmv_cw_chunks;
+                std::vector<ChunkRec> rec((size_t)nch);
+                BMSP_HIP(hipStreamSynchronize(st));
+                copy_d2h_staged(rec.data(), (const char *)A->spmv_cw + A->spmv_cw_off_rec, sizeof(ChunkRec) * (size_t)nch);
+                int64_t slots = 0;
+                for (const ChunkRec &r : rec) slots += ((r.flags & kChHead) ? 1 : 0) + ((r.flags & kChTail) ? 1 : 0);
+                bytes = 8 * nv + (int64_t)sizeof(ChunkRec) * nch + xy + 2 * 8 * as * slots + 8 * A->spmv_cw_split;
+            } else if (vstream_eligible(A)) {
                 build_pos_cache(A, st);
                 const bool cached = A->spmv_pos != nullptr;
                 const char *re = getenv("BMSP_SPMV_RED");
@@ -1208,7 +1506,10 @@ void prepare_spmv(bmsp_matrix_s *A, hipStream_t st)
     if ((size_t)A->values_extent() * es >= (1ull << 32) || (size_t)A->num_cols * es >= (1ull << 32)) return;  // block-row kernel: no plan
     build_plan(A, st);
     const bool rowgroup = A->block_num > 0 && A->nnz >= 16 * A->block_num && A->spmv_plan_long == 0 && !getenv("BMSP_SPMV_NO_ROWGROUP") && pool_owns(A->values);
-    if (vstream_eligible(A) && !rowgroup) build_pos_cache(A, st);
+    if (vstream_eligible(A) && !rowgroup) {
+        build_pos_cache(A, st);
+        if (chunk_wanted(A, 0, (uint32_t)A->num_rows)) build_chunk_cache(A, st);
+    }
 }
 
 // row_lo / row_hi: only rows [row_lo, row_hi) of u are written (the sharded sweep: a rank writes its own slice and nothing else);
