@@ -1093,6 +1093,8 @@ __global__ __launch_bounds__(kThreads) void spmv_rowgroup_kernel(const uint32_t 
 // folded through carry slots: chunk ca parks its 8 partial sums in its TAIL slot, chunks ca+1 .. cb in their HEAD slots; write-through (sc1)
 // stores, drained vmcnt, one agent-scope arrival counter per folded block-row (indexed by ca); the last to arrive sums the slots in chunk
 // order with sc1 loads, writes the 8 rows and resets the counter -- the protocol of the long items above, deterministic, no float atomics.
+// Since round 6 a non-hub chunk first combines each lane's eight values by row in registers and issues one ds_add_f32 per distinct row
+// of the lane (the LDS float adds, paid per active lane, were the largest part of the time after the gathers: DESIGN.md, round 6).
 #ifndef BMSP_CH_V
 #define BMSP_CH_V 512
 #endif
@@ -1178,35 +1180,47 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
 #pragma unroll
     for (int j = 0; j < kChPer; j++) xv[j] = Buf<float>::ld(rx, first + j < nnz ? (w[j] & cmask) * 4u : kOob);
 
+    float pr[kChPer];
+    uint32_t rr[kChPer];
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) {
+        rr[j] = w[j] >> colbits;
+        pr[j] = first + j < nnz ? a[j] * xv[j] : 0.f;
+    }
     if (rc.nwin == 8) {
         // one block-row: eight register sums per lane
         float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < kChPer; j++) {
-            const uint32_t rr = w[j] >> colbits;
-            const float p = first + j < nnz ? a[j] * xv[j] : 0.f;
 #pragma unroll
-            for (int k = 0; k < 8; k++) s[k] += rr == (uint32_t)k ? p : 0.f;
+            for (int k = 0; k < 8; k++) s[k] += rr[j] == (uint32_t)k ? pr[j] : 0.f;
         }
         const float v = chunk_sum8(s, lane);
         if ((lane & 7) == 0) win[((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1)] = v;
     } else {
         for (uint32_t e = (uint32_t)lane; e < rc.nwin; e += 64) win[e] = 0.f;
         __builtin_amdgcn_wave_barrier();
-        // runs of equal rows in registers, one LDS add per run
-        // (the values a lane holds past nnz -- last chunk only -- follow its valid ones: the last valid value ends a run)
-        float run = 0.f;
+        // a lane's values combined by row in registers first (value j joins the first earlier value of its row), then one LDS add per
+        // distinct row of the lane: ds_add_f32 is paid per active lane, and rows repeat inside a lane's eight values beyond runs
+        // (the values a lane holds past nnz -- last chunk only -- add nothing)
+        float acc[kChPer];
+        bool lead[kChPer];
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) acc[j] = pr[j];
 #pragma unroll
         for (int j = 0; j < kChPer; j++) {
-            const uint32_t rr = w[j] >> colbits;
-            const bool on = first + j < nnz;
-            const bool flush = j == kChPer - 1 || first + j + 1 >= nnz || (w[j + (j < kChPer - 1 ? 1 : 0)] >> colbits) != rr;
-            run += on ? a[j] * xv[j] : 0.f;
-            if (flush) {
-                if (on) lds_add(win + rr, run);
-                run = 0.f;
+            bool taken = false;
+#pragma unroll
+            for (int i = 0; i < j; i++) {
+                const bool hit = !taken && rr[i] == rr[j];
+                acc[i] += hit ? acc[j] : 0.f;
+                taken |= hit;
             }
+            lead[j] = !taken;
         }
+#pragma unroll
+        for (int j = 0; j < kChPer; j++)
+            if (lead[j] && first + j < nnz) lds_add(win + rr[j], acc[j]);
     }
     __builtin_amdgcn_wave_barrier();
     // the block-rows this chunk owns (rows before the first value -- chunk 0 -- and after the last are zeros)
