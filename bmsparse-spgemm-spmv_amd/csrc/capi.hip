@@ -338,6 +338,34 @@ int bmsp_matrix_invalidate(bmsp_matrix_t m, int structure_changed)
     BMSP_API_END
 }
 
+int bmsp_matrix_transpose(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    if (out_transposed != 0 && out_transposed != 1) fail(BMSP_ERR_INVALID, "out_transposed must be 0 or 1 (got %d)", out_transposed);
+    need(A, "matrix"); need(out, "out");
+    load_kernels();
+    *out = transpose_matrix(A, out_transposed, true, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_convert_layout(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    if (out_transposed != 0 && out_transposed != 1) fail(BMSP_ERR_INVALID, "out_transposed must be 0 or 1 (got %d)", out_transposed);
+    need(A, "matrix"); need(out, "out");
+    load_kernels();
+    *out = transpose_matrix(A, out_transposed, false, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_copy_values(bmsp_matrix_t A, bmsp_matrix_t out, void *stream)
+{
+    BMSP_API_BEGIN
+    need(A, "matrix"); need(out, "out");
+    copy_values_from(A, out, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_matrix_info(bmsp_matrix_t m, int *num_rows, int *num_cols, int64_t *nnz, int64_t *block_num, bmsp_dtype *dtype, int *transposed)
 {
     BMSP_API_BEGIN

@@ -71,6 +71,11 @@ struct bmsp_matrix_s {
     // a product remembers which operand STRUCTURES it was formed from (struct_hash of A and B; 0 = not stamped: a view, adopted arrays): the
     // fast paths of bmsp_spgemm_numeric trust C only when the stamps match the operands it is given
     uint64_t sp_a_hash = 0, sp_b_hash = 0;
+    // made by bmsp_matrix_transpose / bmsp_matrix_convert_layout: the source's uid (0 = neither), the source tile of every tile (the sort's
+    // payload; null = the source's tile order) and whether values are permuted inside each tile -- what bmsp_matrix_copy_values replays
+    uint64_t tp_src_uid = 0;
+    uint32_t *tp_map = nullptr;
+    int tp_permute = 0;
     uint64_t struct_hash = 0;  // this matrix: sum over its blocks of mix(key, bitmap), + dimensions; 0 = not computed (ensure_struct_hash)
     int values_finite = -1;
     int f32_exp_min = 255, f32_exp_max = 0;  // fp32: biased exponent range of the non-zero stored values (with values_finite)       // fp16 operands of the strip block-MAC: 1 = no inf / NaN stored (-1 = not looked yet)
@@ -178,6 +183,9 @@ void matrix_compare_device(bmsp_matrix_s *m, int64_t nnz, const int *d_rows, con
 bmsp_matrix_s *build_from_device_csr(int num_rows, int num_cols, int64_t nnz, const int *d_row_offsets, const int *d_cols, const double *d_vals,
                                      int transposed, bmsp_dtype dtype, hipStream_t st);
 void free_matrix(bmsp_matrix_s *m);
+// transpose.hip: out = A^T (swap) or A (!swap) with tiles in layout out_transposed; re-gather such an out's values from A
+bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st);
+void copy_values_from(bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

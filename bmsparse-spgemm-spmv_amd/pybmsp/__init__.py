@@ -27,6 +27,7 @@ SYMBOLS = [
     "bmsp_event_create", "bmsp_event_record", "bmsp_event_elapsed_ms", "bmsp_event_destroy",
     "bmsp_matrix_from_mtx", "bmsp_matrix_from_coo", "bmsp_matrix_from_coo_device", "bmsp_matrix_from_arrays",
     "bmsp_matrix_save", "bmsp_matrix_load", "bmsp_matrix_free", "bmsp_matrix_prepare", "bmsp_matrix_invalidate", "bmsp_matrix_info", "bmsp_matrix_arrays", "bmsp_matrix_block_row_ptr",
+    "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values",
     "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmm", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
@@ -101,6 +102,9 @@ def lib():
         L.bmsp_matrix_info.argtypes = [vp, p(i), p(i), p(i64), p(i64), p(i), p(i)]
         L.bmsp_matrix_arrays.argtypes = [vp, p(vp), p(vp), p(vp), p(vp)]
         L.bmsp_matrix_block_row_ptr.argtypes = [vp, p(vp), p(i64)]
+        L.bmsp_matrix_transpose.argtypes = [vp, i, vp, p(vp)]
+        L.bmsp_matrix_convert_layout.argtypes = [vp, i, vp, p(vp)]
+        L.bmsp_matrix_copy_values.argtypes = [vp, vp, vp]
         L.bmsp_matrix_to_coo_host.argtypes = [vp, vp, vp, vp]
         L.bmsp_matrix_to_coo_device.argtypes = [vp, vp, vp, vp, vp]
         L.bmsp_matrix_to_csr_device.argtypes = [vp, vp, vp, vp, vp]
@@ -341,6 +345,23 @@ class BmSpMatrix:
         p, n = C.c_void_p(), C.c_int64()
         check(lib().bmsp_matrix_block_row_ptr(self.h, C.byref(p), C.byref(n)))
         return DeviceArray(n.value + 1, np.uint32, p.value, self).to_host()
+
+    def transpose(self, transposed=False, stream=None):
+        """A^T as a new matrix with its tiles in layout `transposed` (bmsp_matrix_transpose): no COO round trip."""
+        h = C.c_void_p()
+        check(lib().bmsp_matrix_transpose(self.h, int(bool(transposed)), stream, C.byref(h)))
+        return BmSpMatrix(h.value)
+
+    def with_layout(self, transposed, stream=None):
+        """this matrix with its tiles in layout `transposed` (bmsp_matrix_convert_layout; a copy when it already has it)."""
+        h = C.c_void_p()
+        check(lib().bmsp_matrix_convert_layout(self.h, int(bool(transposed)), stream, C.byref(h)))
+        return BmSpMatrix(h.value)
+
+    def copy_values_from(self, src, stream=None):
+        """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
+        check(lib().bmsp_matrix_copy_values(src.h, self.h, stream))
+        return self
 
     # generate_coo()
     def to_coo(self):

@@ -190,6 +190,26 @@ public:
     }
     bmsp_matrix_t handle() const { return h_; }
 
+    /* A^T (num_cols x num_rows) with its tiles column-major when transposed_layout (bmsp_matrix_transpose) */
+    bmSpMatrix<valueType> transpose(bool transposed_layout) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_transpose(h_, transposed_layout ? 1 : 0, nullptr, &t));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+    /* the same matrix with its tiles column-major when transposed_layout (bmsp_matrix_convert_layout): the right operand of
+     * bmSparse_mult from a left one, `bmSpMatrix<half> B = A.with_layout(true);` instead of parsing the file twice */
+    bmSpMatrix<valueType> with_layout(bool transposed_layout) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_convert_layout(h_, transposed_layout ? 1 : 0, nullptr, &t));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+
     /* src/bmSpMatrix.cu:320-363 */
     void generate_coo()
     {

@@ -116,6 +116,21 @@ int bmsp_matrix_arrays(bmsp_matrix_t m, uint64_t **d_keys, uint64_t **d_bmps, ui
  * after changing keys / bitmaps / offsets call it with structure_changed = 1 (drops the block-row pointer, SpMV plan and position
  * cache, block records too).  Synchronises the device.  SpMV reads values directly: a value-only update needs no call for it. */
 int bmsp_matrix_invalidate(bmsp_matrix_t m, int structure_changed);
+/* Transpose and tile-layout conversion of a matrix already on the device (no COO round trip).  `out_transposed` is the layout of
+ * the output's tiles, as the builders' flag: 0 row-major, 1 column-major (the right operand of bmsp_spgemm).  The output is a fresh
+ * pool-owned handle whose four arrays equal, bit for bit, what the builders make from the swapped COO (transpose) or the same COO
+ * (convert_layout) in that layout; offsets hold block_num+1 entries.  Values move as raw bits (-0, Inf, NaN payloads and subnormals
+ * survive), every stored entry is kept, A and its caches are untouched.  Row-panel views are refused.  Work runs on `stream`; the
+ * calls synchronise it before they return.
+ *   bmsp_matrix_transpose:      out = A^T (num_cols x num_rows).  Into the other layout it only re-orders whole tiles.
+ *   bmsp_matrix_convert_layout: out = A with tiles in layout out_transposed (a copy when A already has that layout).
+ *   bmsp_matrix_copy_values:    `out` was made from A by one of the two calls above and A's STRUCTURE has not changed since (its
+ *       uid, renewed by bmsp_matrix_invalidate(A, 1)): re-gathers out's values from A's current values in one pass, no sort; otherwise
+ *       BMSP_ERR_INVALID.  Drops out's value-derived caches as bmsp_matrix_invalidate(out, 0) would; asynchronous on `stream` unless
+ *       out holds such caches (dropping them synchronises the device). */
+int bmsp_matrix_transpose(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out);
+int bmsp_matrix_convert_layout(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out);
+int bmsp_matrix_copy_values(bmsp_matrix_t A, bmsp_matrix_t out, void *stream);
 /* dense block-row pointer (num_block_rows+1 uint32 entries) the operators use; built once and cached
  * (the reference rebuilds a compressed one on every call, src/bmSparse_SPMV.cu:199-206). */
 int bmsp_matrix_block_row_ptr(bmsp_matrix_t m, const uint32_t **d_rowptr, int64_t *num_block_rows);
