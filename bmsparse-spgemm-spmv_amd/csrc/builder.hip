@@ -384,6 +384,7 @@ void free_matrix(bmsp_matrix_s *m)
     pool_free(m->csr_rowptr); pool_free(m->csr_ent);
     pool_free(m->sp_tasks); pool_free(m->sp_task_begin); pool_free(m->sp_c_of_wave);
     pool_free(m->tp_map);
+    pool_free(m->add_map);
     free_matrix(m->shard_view);
     delete m;
 }
@@ -415,6 +416,7 @@ void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)
     pool_free(m->col_index); pool_free(m->col_index_row); m->col_index = nullptr; m->col_index_row = nullptr; m->col_index_tried = 0;
     pool_free(m->col_mass); m->col_mass = nullptr;
     pool_free(m->tp_map); m->tp_map = nullptr; m->tp_src_uid = 0; m->tp_permute = 0;
+    pool_free(m->add_map); m->add_map = nullptr; m->add_a_uid = 0; m->add_b_uid = 0;
     free_matrix(m->shard_view); m->shard_view = nullptr; m->shard_world = 0; m->shard_rank = 0; m->shard_bounds.clear();
 }
 

@@ -366,6 +366,24 @@ int bmsp_matrix_copy_values(bmsp_matrix_t A, bmsp_matrix_t out, void *stream)
     BMSP_API_END
 }
 
+int bmsp_matrix_add(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, int out_transposed, void *stream, bmsp_matrix_t *C)
+{
+    BMSP_API_BEGIN
+    if (out_transposed != 0 && out_transposed != 1) fail(BMSP_ERR_INVALID, "out_transposed must be 0 or 1 (got %d)", out_transposed);
+    need(A, "matrix A"); need(B, "matrix B"); need(C, "output C");
+    load_kernels();
+    *C = add_matrices(alpha, A, beta, B, out_transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_add_values(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, bmsp_matrix_t C, void *stream)
+{
+    BMSP_API_BEGIN
+    need(A, "matrix A"); need(B, "matrix B"); need(C, "matrix C");
+    add_values(alpha, A, beta, B, C, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_matrix_info(bmsp_matrix_t m, int *num_rows, int *num_cols, int64_t *nnz, int64_t *block_num, bmsp_dtype *dtype, int *transposed)
 {
     BMSP_API_BEGIN

@@ -76,6 +76,10 @@ struct bmsp_matrix_s {
     uint64_t tp_src_uid = 0;
     uint32_t *tp_map = nullptr;
     int tp_permute = 0;
+    // made by bmsp_matrix_add: the operands' uids (0 = not a sum) and, per tile, its A tile (add_map[c]) and its B tile (add_map[block_num + c];
+    // ~0u = none) -- what bmsp_matrix_add_values replays
+    uint64_t add_a_uid = 0, add_b_uid = 0;
+    uint32_t *add_map = nullptr;
     uint64_t struct_hash = 0;  // this matrix: sum over its blocks of mix(key, bitmap), + dimensions; 0 = not computed (ensure_struct_hash)
     int values_finite = -1;
     int f32_exp_min = 255, f32_exp_max = 0;  // fp32: biased exponent range of the non-zero stored values (with values_finite)       // fp16 operands of the strip block-MAC: 1 = no inf / NaN stored (-1 = not looked yet)
@@ -186,6 +190,9 @@ void free_matrix(bmsp_matrix_s *m);
 // transpose.hip: out = A^T (swap) or A (!swap) with tiles in layout out_transposed; re-gather such an out's values from A
 bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st);
 void copy_values_from(bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
+// add.hip: C = alpha*A + beta*B with tiles in layout out_transposed; re-compute such a C's values from the same two structures
+bmsp_matrix_s *add_matrices(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, int out_transposed, hipStream_t st);
+void add_values(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -27,7 +27,7 @@ SYMBOLS = [
     "bmsp_event_create", "bmsp_event_record", "bmsp_event_elapsed_ms", "bmsp_event_destroy",
     "bmsp_matrix_from_mtx", "bmsp_matrix_from_coo", "bmsp_matrix_from_coo_device", "bmsp_matrix_from_arrays",
     "bmsp_matrix_save", "bmsp_matrix_load", "bmsp_matrix_free", "bmsp_matrix_prepare", "bmsp_matrix_invalidate", "bmsp_matrix_info", "bmsp_matrix_arrays", "bmsp_matrix_block_row_ptr",
-    "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values",
+    "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmm", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
@@ -105,6 +105,8 @@ def lib():
         L.bmsp_matrix_transpose.argtypes = [vp, i, vp, p(vp)]
         L.bmsp_matrix_convert_layout.argtypes = [vp, i, vp, p(vp)]
         L.bmsp_matrix_copy_values.argtypes = [vp, vp, vp]
+        L.bmsp_matrix_add.argtypes = [C.c_double, vp, C.c_double, vp, i, vp, p(vp)]
+        L.bmsp_matrix_add_values.argtypes = [C.c_double, vp, C.c_double, vp, vp, vp]
         L.bmsp_matrix_to_coo_host.argtypes = [vp, vp, vp, vp]
         L.bmsp_matrix_to_coo_device.argtypes = [vp, vp, vp, vp, vp]
         L.bmsp_matrix_to_csr_device.argtypes = [vp, vp, vp, vp, vp]
@@ -422,6 +424,20 @@ class BmSpMatrix:
             self.free()
         except Exception:
             pass
+
+
+def add(A, B, alpha=1.0, beta=1.0, transposed=None, stream=None):
+    """alpha*A + beta*B as a new matrix (bmsp_matrix_add), its tiles in layout `transposed` (None: A's layout)."""
+    lay = A.info()["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_add(float(alpha), A.h, float(beta), B.h, lay, stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def add_values(Cm, A, B, alpha=1.0, beta=1.0, stream=None):
+    """re-computes the values of Cm = add(A, B, ...) from A's and B's current values (bmsp_matrix_add_values)."""
+    check(lib().bmsp_matrix_add_values(float(alpha), A.h, float(beta), B.h, Cm.h, stream))
+    return Cm
 
 
 # bmSparse_SpMV(A, v, u, batched)

@@ -286,6 +286,22 @@ inline void bmSparse_mult_numeric(bmSpMatrix<valueIn> &A, bmSpMatrix<valueIn> &B
     bmsp::check(bmsp_spgemm_numeric(A.handle(), B.handle(), C.handle(), (int)tc_version, nullptr, stats));
 }
 
+/* C = alpha*A + beta*B (bmsp_matrix_add): C's tiles column-major when transposed_layout.  A and B share shape and value type; either
+ * layout.  _values re-computes C's values after A's or B's values changed in place (same structures, same order; bmsp_matrix_add_values). */
+template <class valueType>
+inline void bmSparse_add(double alpha, bmSpMatrix<valueType> &A, double beta, bmSpMatrix<valueType> &B, bmSpMatrix<valueType> &C,
+                         bool transposed_layout = false)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_matrix_add(alpha, A.handle(), beta, B.handle(), transposed_layout ? 1 : 0, nullptr, &c));
+    C.reset(c);
+}
+template <class valueType>
+inline void bmSparse_add_values(double alpha, bmSpMatrix<valueType> &A, double beta, bmSpMatrix<valueType> &B, bmSpMatrix<valueType> &C)
+{
+    bmsp::check(bmsp_matrix_add_values(alpha, A.handle(), beta, B.handle(), C.handle(), nullptr));
+}
+
 /* The same product sharded over one process per GPU (bmsp_spgemm_sharded): every rank passes the same A and B, multiplies
  * its block-row panel of A and returns the whole C. */
 template <class valueIn, class valueOut>

@@ -131,6 +131,26 @@ int bmsp_matrix_invalidate(bmsp_matrix_t m, int structure_changed);
 int bmsp_matrix_transpose(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out);
 int bmsp_matrix_convert_layout(bmsp_matrix_t A, int out_transposed, void *stream, bmsp_matrix_t *out);
 int bmsp_matrix_copy_values(bmsp_matrix_t A, bmsp_matrix_t out, void *stream);
+/* Sparse addition C = alpha*A + beta*B of two matrices on the device (no COO round trip).  A and B have the same shape and dtype (F32,
+ * F16 or F64); either may use either tile layout; `out_transposed` is C's layout (0 row-major, 1 column-major).
+ *   Structure: C's tiles are the union of A's and B's tile keys; each C bitmap is the OR of the operands' bitmaps in C's layout.  Every
+ *       coordinate stored in A or B is stored in C, numeric cancellation included (A + (-A) has A's structure with stored zeros).  The
+ *       four arrays equal, bit for bit, what the builders make from the concatenated COO [A's entries; B's entries] in that layout;
+ *       offsets hold block_num+1 entries.
+ *   Values (never a fused multiply-add): F32 c = fl32(fl32(alpha*a) + fl32(beta*b)) with alpha, beta rounded once to fp32; an entry of
+ *       one operand only is fl32(alpha*a) or fl32(beta*b).  F64 the same in double.  F16: products and sum in fp32 as for F32, then one
+ *       round-to-nearest-even to fp16 (it may overflow to +-Inf).  Subnormals are kept.
+ *   An operand in the other layout is read through its transposed bitmap inside the value pass (no conversion, no copy).  A and B are
+ *   never modified (they may be the same handle); their block-row pointers are built if missing.  Refused with BMSP_ERR_INVALID: null
+ *   handles / output pointer, out_transposed not 0 / 1, shapes or dtypes that differ, row-panel views.  BMSP_ERR_LIMIT: A and B hold
+ *   2^32 - 1 tiles or more together (C's 32-bit tile maps), or B holds 2^32 values or more.
+ *   bmsp_matrix_add:        a fresh pool-owned C; runs on `stream` and synchronises it before it returns (C's tile count is read back).
+ *   bmsp_matrix_add_values: C was made by bmsp_matrix_add from these two operands, in this order, and neither operand's STRUCTURE changed
+ *       since (their uids, renewed by bmsp_matrix_invalidate(X, 1)): re-computes C's values from A's and B's current values with this
+ *       alpha and beta in one pass, no merge; otherwise BMSP_ERR_INVALID.  Drops C's value-derived caches as bmsp_matrix_copy_values
+ *       does; asynchronous on `stream` unless C holds such caches (dropping them synchronises the device). */
+int bmsp_matrix_add(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, int out_transposed, void *stream, bmsp_matrix_t *C);
+int bmsp_matrix_add_values(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, bmsp_matrix_t C, void *stream);
 /* dense block-row pointer (num_block_rows+1 uint32 entries) the operators use; built once and cached
  * (the reference rebuilds a compressed one on every call, src/bmSparse_SPMV.cu:199-206). */
 int bmsp_matrix_block_row_ptr(bmsp_matrix_t m, const uint32_t **d_rowptr, int64_t *num_block_rows);
