@@ -1086,15 +1086,15 @@ __global__ __launch_bounds__(kThreads) void spmv_rowgroup_kernel(const uint32_t 
 // each).  The x gathers follow back to back -- one round trip, then the gathers, then the reduction:
 //   * a chunk inside ONE block-row (hub block-rows: most of a graph's values) keeps eight register sums per lane, reduced by a halving
 //     exchange (10 shuffles) into the eight row sums;
-//   * any other chunk adds runs of equal rows in registers (a lane's eight values are consecutive) and then one ds_add_f32 per run into an
-//     LDS window over the chunk's block-rows (kChWin rows at most).
+//   * any other chunk reduces by block-row in registers (chunk_seg_reduce: per-lane block-row sums, a DPP segmented scan across lanes) and
+//     writes each block-row's 8 sums once, with plain stores, into an LDS window over the chunk's block-rows (kChWin rows at most).
 // Every row is written once.  Chunk c owns the block-rows from its first one (exclusive when that block-row began in an earlier chunk) up to
 // chunk c+1's first block-row -- empty block-rows included, written as zeros.  A block-row whose values lie in several chunks (ca .. cb) is
 // folded through carry slots: chunk ca parks its 8 partial sums in its TAIL slot, chunks ca+1 .. cb in their HEAD slots; write-through (sc1)
 // stores, drained vmcnt, one agent-scope arrival counter per folded block-row (indexed by ca); the last to arrive sums the slots in chunk
 // order with sc1 loads, writes the 8 rows and resets the counter -- the protocol of the long items above, deterministic, no float atomics.
-// Since round 6 a non-hub chunk first combines each lane's eight values by row in registers and issues one ds_add_f32 per distinct row
-// of the lane (the LDS float adds, paid per active lane, were the largest part of the time after the gathers: DESIGN.md, round 6).
+// Round 6 combined each lane's values by row before one ds_add_f32 per distinct row; since round 7 no LDS float add is left: ds_add_f32
+// is paid per active lane and was the largest part of the time after the gathers (rounds 6 and 7).
 #ifndef BMSP_CH_V
 #define BMSP_CH_V 512
 #endif
@@ -1130,6 +1130,75 @@ __device__ __forceinline__ float chunk_sum8(const float (&s)[8], int lane)
     return v;
 }
 
+__device__ __forceinline__ void chunk_put8(float *p, const float (&v)[8])
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    *(f4 *)p = f4{v[0], v[1], v[2], v[3]};
+    *(f4 *)(p + 4) = f4{v[4], v[5], v[6], v[7]};
+}
+
+// one step of wave_run_sum over eight sums at once: a lane whose DPP source lane holds the same key adds that lane's sums; false (and
+// nothing done) when no lane of the wave does -- keys are non-decreasing, so no later in-row step would either
+template <int CTRL, int ROWS>
+__device__ __forceinline__ bool chunk_scan_step(float (&t)[8], uint32_t key)
+{
+    const bool m = dpp_u32<CTRL, ROWS>(~0u, key) == key;
+    if (!__builtin_amdgcn_ballot_w64(m)) return false;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const float n = t[k] + dpp_val<CTRL, ROWS>(0.f, t[k]);
+        t[k] = m ? n : t[k];
+    }
+    return true;
+}
+
+// the reduction of a chunk over several block-rows (round 7): rk[] are rows relative to the chunk's first block-row, their block-rows
+// (rk >> 3) non-decreasing across a lane's values and across lanes; win is zero-filled (empty block-rows).  Every block-row present is
+// written once, as its 8 row sums, with plain LDS stores by the lane where it ends: no LDS float atomics.
+//   in-lane: 8 register sums for the current block-row; where the block-row changes they become the lane's head (its first block-row)
+//     or, for a block-row that begins and ends in the lane, go straight to the window; what is left is the lane's tail (last block-row);
+//   cross-lane: an inclusive segmented scan of the tail sums keyed by the tail block-row (row_shr inside rows of 16, then row_bcast), and
+//     a head that continues the left lane's tail block-row adds that lane's scanned sums.
+// The sums run in a fixed order (storage order inside a lane, then the scan's fixed tree), so y is reproducible bit for bit.
+__device__ __forceinline__ void chunk_seg_reduce(float *win, const uint32_t (&rk)[kChPer], const float (&pr)[kChPer])
+{
+    const uint32_t bf = rk[0] >> 3, bl = rk[kChPer - 1] >> 3;
+    float h[8], t[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) h[k] = t[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) {
+        if (j > 0 && (rk[j] >> 3) != (rk[j - 1] >> 3)) {
+            const uint32_t bp = rk[j - 1] >> 3;
+            if (bp == bf) {
+#pragma unroll
+                for (int k = 0; k < 8; k++) h[k] = t[k];
+            } else {
+                chunk_put8(win + 8u * bp, t);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) t[k] = 0.f;
+        }
+        const uint32_t r = rk[j] & 7u;
+#pragma unroll
+        for (int k = 0; k < 8; k++) t[k] += r == (uint32_t)k ? pr[j] : 0.f;
+    }
+    if (chunk_scan_step<0x111, 0xf>(t, bl) && chunk_scan_step<0x112, 0xf>(t, bl) && chunk_scan_step<0x114, 0xf>(t, bl)) chunk_scan_step<0x118, 0xf>(t, bl);
+    chunk_scan_step<0x142, 0xa>(t, bl);  // row_bcast:15 into rows 1 and 3
+    chunk_scan_step<0x143, 0xc>(t, bl);  // row_bcast:31 into rows 2 and 3
+    const uint32_t bl_left = dpp_u32<0x138>(~0u, bl), bf_right = dpp_u32<0x130>(~0u, bf);  // wave_shr:1, wave_shl:1
+    float tl[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) tl[k] = dpp_val<0x138>(0.f, t[k]);
+    if (bf != bl) {
+        const bool cont = bl_left == bf;
+#pragma unroll
+        for (int k = 0; k < 8; k++) h[k] = cont ? h[k] + tl[k] : h[k];
+        chunk_put8(win + 8u * bf, h);
+    }
+    if (bf_right != bl) chunk_put8(win + 8u * bl, t);
+}
+
 // the last of chunks ca .. cb to arrive: slot (ca, tail) + slots (ca+1 .. cb, head), in chunk order
 __device__ __forceinline__ void chunk_fold(const float *__restrict__ carry, float *__restrict__ y, uint32_t *__restrict__ counters, uint32_t ca,
                                            uint32_t cb, uint32_t br, uint32_t num_rows, int lane)
@@ -1152,7 +1221,7 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
 {
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    __shared__ float win[kChWin];
+    __shared__ __attribute__((aligned(16))) float win[kChWin];
     const int lane = lane_id();
     const uint32_t c = blockIdx.x;
     const ChunkRec rc = recs[c];
@@ -1184,7 +1253,7 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
     uint32_t rr[kChPer];
 #pragma unroll
     for (int j = 0; j < kChPer; j++) {
-        rr[j] = w[j] >> colbits;
+        rr[j] = first + j < nnz ? w[j] >> colbits : rc.nwin - 8u;  // past nnz (last chunk only): the last block-row, adding 0
         pr[j] = first + j < nnz ? a[j] * xv[j] : 0.f;
     }
     if (rc.nwin == 8) {
@@ -1200,27 +1269,7 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
     } else {
         for (uint32_t e = (uint32_t)lane; e < rc.nwin; e += 64) win[e] = 0.f;
         __builtin_amdgcn_wave_barrier();
-        // a lane's values combined by row in registers first (value j joins the first earlier value of its row), then one LDS add per
-        // distinct row of the lane: ds_add_f32 is paid per active lane, and rows repeat inside a lane's eight values beyond runs
-        // (the values a lane holds past nnz -- last chunk only -- add nothing)
-        float acc[kChPer];
-        bool lead[kChPer];
-#pragma unroll
-        for (int j = 0; j < kChPer; j++) acc[j] = pr[j];
-#pragma unroll
-        for (int j = 0; j < kChPer; j++) {
-            bool taken = false;
-#pragma unroll
-            for (int i = 0; i < j; i++) {
-                const bool hit = !taken && rr[i] == rr[j];
-                acc[i] += hit ? acc[j] : 0.f;
-                taken |= hit;
-            }
-            lead[j] = !taken;
-        }
-#pragma unroll
-        for (int j = 0; j < kChPer; j++)
-            if (lead[j] && first + j < nnz) lds_add(win + rr[j], acc[j]);
+        chunk_seg_reduce(win, rr, pr);
     }
     __builtin_amdgcn_wave_barrier();
     // the block-rows this chunk owns (rows before the first value -- chunk 0 -- and after the last are zeros)
