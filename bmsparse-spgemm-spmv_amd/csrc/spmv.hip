@@ -1199,18 +1199,45 @@ __device__ __forceinline__ void chunk_seg_reduce(float *win, const uint32_t (&rk
     if (bf_right != bl) chunk_put8(win + 8u * bl, t);
 }
 
-// the last of chunks ca .. cb to arrive: slot (ca, tail) + slots (ca+1 .. cb, head), in chunk order
+// U slots per lane of the fold, chunks kb + g, kb + g + 8, ... (those past cb load slot cb again and add 0): every load issued before the
+// first wait (a load under a per-element condition would be branched around and waited for one by one)
+template <int U>
+__device__ __forceinline__ float chunk_fold_batch(const float *__restrict__ carry, uint32_t ca, uint32_t kb, uint32_t cb, uint32_t r, uint32_t g)
+{
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t k = min(kb + g + 8u * (uint32_t)u, cb);
+        v[u] = __hip_atomic_load(&carry[((size_t)k * 2 + (k == ca ? 1 : 0)) * 8 + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < U; u++) s += kb + g + 8u * (uint32_t)u <= cb ? v[u] : 0.f;
+    return s;
+}
+
+// the last of chunks ca .. cb to arrive: slot (ca, tail) + slots (ca+1 .. cb, head).  Lane (row r = lane / 8, group g = lane % 8) sums
+// the slots of chunks ca + g + 8i, up to 32 chunks per batch of loads in flight (round 8: the old loop waited for each load), then the
+// 8 groups of a row combine by DPP (row_shr 1, 2, 4: lane 8r + 7 ends with the row sum).  The order is fixed by ca and cb alone, so
+// repeated sweeps are bitwise equal.
 __device__ __forceinline__ void chunk_fold(const float *__restrict__ carry, float *__restrict__ y, uint32_t *__restrict__ counters, uint32_t ca,
                                            uint32_t cb, uint32_t br, uint32_t num_rows, int lane)
 {
-    const int r = lane & 7, g = lane >> 3;
-    float sum = 0.f;
-    for (uint32_t k = ca + (uint32_t)g; k <= cb; k += 8)
-        sum += __hip_atomic_load(&carry[((size_t)k * 2 + (k == ca ? 1 : 0)) * 8 + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int d = 8; d < 64; d <<= 1) sum += __shfl_xor(sum, d, kWave);
-    const uint32_t row = br * 8u + (uint32_t)r;
-    if (g == 0 && row < num_rows) y[row] = sum;
+    const uint32_t r = (uint32_t)lane >> 3, g = (uint32_t)lane & 7u, n = cb - ca + 1u;
+    float sum;
+    if (n <= 8u) {
+        sum = chunk_fold_batch<1>(carry, ca, ca, cb, r, g);
+    } else if (n <= 16u) {
+        sum = chunk_fold_batch<2>(carry, ca, ca, cb, r, g);
+    } else {
+        sum = 0.f;
+        for (uint32_t kb = ca; kb <= cb; kb += 32u) sum += chunk_fold_batch<4>(carry, ca, kb, cb, r, g);
+    }
+    sum += dpp_val<0x111>(0.f, sum);  // row_shr:1
+    sum += dpp_val<0x112>(0.f, sum);  // row_shr:2
+    sum += dpp_val<0x114>(0.f, sum);  // row_shr:4
+    const uint32_t row = br * 8u + r;
+    if (g == 7u && row < num_rows) y[row] = sum;
     if (lane == 0) __hip_atomic_store(&counters[ca], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -1272,6 +1299,18 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
         chunk_seg_reduce(win, rr, pr);
     }
     __builtin_amdgcn_wave_barrier();
+    // folded block-rows: park the 8 partial sums, drain them, then take both tickets with ONE returning atomic -- lanes 0 (head) and 1
+    // (tail) at lane-dependent addresses; two uniform-address atomics were each rewritten into a wave-reduced atomic and waited for in
+    // turn (round 8).  The own-row y stores go out behind the ticket and overlap its round trip.
+    uint32_t ticket = 0;
+    if (rc.flags) {
+        if ((rc.flags & kChHead) && lane < 8) __hip_atomic_store(&carry[((size_t)c * 2) * 8 + lane], win[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((rc.flags & kChTail) && lane < 8)
+            __hip_atomic_store(&carry[((size_t)c * 2 + 1) * 8 + lane], win[rc.nwin - 8u + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0 ? (rc.flags & kChHead) != 0u : lane == 1 && (rc.flags & kChTail) != 0u)
+            ticket = __hip_atomic_fetch_add(&counters[lane == 0 ? rc.head_ca : c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     // the block-rows this chunk owns (rows before the first value -- chunk 0 -- and after the last are zeros)
     const int32_t base = (int32_t)(rc.fb * 8u);
     const uint32_t row_end = min(rc.own_e * 8u, num_rows);
@@ -1280,14 +1319,6 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
         y[row] = rel >= 0 && rel < (int32_t)rc.nwin ? win[rel] : 0.f;
     }
     if (!rc.flags) return;
-    // folded block-rows: park the 8 partial sums, the last arriver folds
-    if ((rc.flags & kChHead) && lane < 8) __hip_atomic_store(&carry[((size_t)c * 2) * 8 + lane], win[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((rc.flags & kChTail) && lane < 8)
-        __hip_atomic_store(&carry[((size_t)c * 2 + 1) * 8 + lane], win[rc.nwin - 8u + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    uint32_t ticket = 0;
-    if (lane == 0 && (rc.flags & kChHead)) ticket = __hip_atomic_fetch_add(&counters[rc.head_ca], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 1 && (rc.flags & kChTail)) ticket = __hip_atomic_fetch_add(&counters[c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t th = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 0), tt = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 1);
     if ((rc.flags & kChHead) && th == rc.head_cb - rc.head_ca) chunk_fold(carry, y, counters, rc.head_ca, rc.head_cb, rc.fb, num_rows, lane);
     if ((rc.flags & kChTail) && tt == rc.tail_cb - c) chunk_fold(carry, y, counters, c, rc.tail_cb, rc.fb + rc.nwin / 8u - 1u, num_rows, lane);
