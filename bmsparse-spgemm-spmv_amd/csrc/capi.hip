@@ -384,6 +384,27 @@ int bmsp_matrix_add_values(double alpha, bmsp_matrix_t A, double beta, bmsp_matr
     BMSP_API_END
 }
 
+int bmsp_matrix_prune(bmsp_matrix_t A, int rule, double tol, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
+                      bmsp_prune_stats *stats)
+{
+    BMSP_API_BEGIN
+    prune_check_args(rule, tol, flags, out_transposed);
+    if (!out && !stats) fail(BMSP_ERR_INVALID, "out and stats are both null");
+    need(A, "matrix A");
+    load_kernels();
+    prune_matrix(A, rule, tol, flags, out_transposed, as_stream(stream), out, stats);
+    BMSP_API_END
+}
+
+int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream)
+{
+    BMSP_API_BEGIN
+    need(A, "matrix A"); need(d_rowmax, "d_rowmax");
+    load_kernels();
+    row_absmax(A, d_rowmax, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_matrix_info(bmsp_matrix_t m, int *num_rows, int *num_cols, int64_t *nnz, int64_t *block_num, bmsp_dtype *dtype, int *transposed)
 {
     BMSP_API_BEGIN

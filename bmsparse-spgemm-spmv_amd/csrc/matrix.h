@@ -193,6 +193,11 @@ void copy_values_from(bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
 // add.hip: C = alpha*A + beta*B with tiles in layout out_transposed; re-compute such a C's values from the same two structures
 bmsp_matrix_s *add_matrices(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, int out_transposed, hipStream_t st);
 void add_values(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
+// prune.hip: *out = A without the entries the rule drops (tiles in layout out_transposed) and / or the counts; the row maxima of |v|
+void prune_check_args(int rule, double tol, int flags, int out_transposed);
+void prune_matrix(bmsp_matrix_s *A, int rule, double tol, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
+                  bmsp_prune_stats *stats);
+void row_absmax(bmsp_matrix_s *A, void *d_rowmax, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -1,0 +1,372 @@
+// prune.hip -- drops stored entries of a matrix already on the device (bmsp_matrix_prune / bmsp_matrix_row_absmax), without going back
+// through scalar COO entries.
+//
+// An entry goes iff |v| <= tol (BMSP_PRUNE_ABS) or |v| <= tol * rowmax(its row) (BMSP_PRUNE_ROW_REL), compared in double on the exactly
+// widened stored value; NaN is never dropped (the comparison is false).  Tiles keep their order and their keys in both layouts, so the
+// output is a COMPACTION of A's tile list: nothing is sorted, nothing is searched.
+//
+// Passes:
+//   rowmax  (ROW_REL, row_absmax) G lanes per tile: a lane takes the maximum of |v| over the rows of its tile (all eight, or row t of
+//           eight lanes), as the BITS of the non-negative value (they order as unsigned integers; NaN bits lie above +Inf and are
+//           skipped).  The tiles of a block-row are neighbours in the tile list, so the lanes of a wave that hold the same block-row
+//           combine with a segmented shuffle scan and only the last of them issues an integer atomic max per row: a hub block-row of
+//           n tiles costs n / 64 (G = 1) or n / 8 (G = 8) atomics per row, not n.  Max is exact and order-independent.
+//   mark    G lanes per tile: the kept bitmap in A's layout (G = 8: a lane per bitmap byte, OR'd across the eight lanes).  The diagonal
+//           of a tile with block_row == block_col is the positions 0, 9, .., 63 in either layout.
+//   scan    one exclusive scan of {tile kept ? 1 : 0 (low 32 bits), kept values (high 32 bits)}: slot and value offset of every kept
+//           tile at once (a transposed bitmap has the same popcount, so the offsets need no second scan).  The total is read back: the one
+//           synchronisation in the middle; count-only calls end here.
+//   place   G lanes per tile of A: a kept tile writes its key, kept bitmap (transposed when the layout flips) and offset at its slot and
+//           compacts its kept values there; values move as raw bits.
+#include "matrix.h"
+#include "prims.hip.h"
+#include <cmath>
+#include <cstdlib>
+#include <memory>
+
+namespace bmsp {
+namespace {
+
+constexpr uint64_t kTileDiagonal = 0x8040201008040201ull;  // positions 9k: row k, column k of a tile in either layout
+
+__device__ __forceinline__ int transposed_pos(int p) { return ((p & 7) << 3) | (p >> 3); }
+__device__ __forceinline__ uint64_t byte_mask(int t) { return 0xff00000000000000ull >> (8 * t); }
+
+// storage type S of a dtype: R the type of its row maxima (bmsp_spmv's convention for u), U the bits of an R
+template <typename S>
+struct PruneType;
+template <>
+struct PruneType<float> {
+    using R = float;
+    using U = uint32_t;
+    static constexpr U kInf = 0x7f800000u;
+    static __device__ __forceinline__ U abs_bits(float s) { return __builtin_bit_cast(uint32_t, s) & 0x7fffffffu; }
+    static __device__ __forceinline__ double widen(float s) { return (double)s; }
+};
+template <>
+struct PruneType<uint16_t> {
+    using R = float;
+    using U = uint32_t;
+    static constexpr U kInf = 0x7f800000u;
+    static __device__ __forceinline__ U abs_bits(uint16_t s)
+    {
+        return __builtin_bit_cast(uint32_t, (float)__builtin_bit_cast(_Float16, (uint16_t)(s & 0x7fffu)));
+    }
+    static __device__ __forceinline__ double widen(uint16_t s) { return (double)__builtin_bit_cast(_Float16, s); }
+};
+template <>
+struct PruneType<double> {
+    using R = double;
+    using U = uint64_t;
+    static constexpr U kInf = 0x7ff0000000000000ull;
+    static __device__ __forceinline__ U abs_bits(double s) { return __builtin_bit_cast(uint64_t, s) & 0x7fffffffffffffffull; }
+    static __device__ __forceinline__ double widen(double s) { return s; }
+};
+
+__device__ __forceinline__ void atomic_max_bits(uint32_t *p, uint32_t v) { atomicMax(p, v); }
+__device__ __forceinline__ void atomic_max_bits(uint64_t *p, uint64_t v) { atomicMax((unsigned long long *)p, (unsigned long long)v); }
+
+// rowmax[row] = max(rowmax[row], max |v| over the non-NaN stored entries of the row), as bits; the caller zeroes rowmax (num_rows entries).
+// Every lane stays to the end: the shuffles need the whole wave.
+template <typename S, int G>
+__global__ __launch_bounds__(kThreads) void row_absmax_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ bmps,
+                                                              const uint64_t *__restrict__ offsets, const S *__restrict__ vals, uint64_t nb,
+                                                              int flip, int64_t num_rows, typename PruneType<S>::U *__restrict__ rowmax)
+{
+    using P = PruneType<S>;
+    using U = typename P::U;
+    constexpr int R = 8 / G;  // rows of the tile a lane takes
+    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t j = gid / G;
+    const int t = (int)(gid % G);
+    const bool live = j < nb;
+    uint32_t brow = ~0u;
+    U m[R];
+#pragma unroll
+    for (int i = 0; i < R; i++) m[i] = 0;
+    if (live) {
+        brow = key_row(keys[j]);
+        const uint64_t ib = bmps[j];
+        const uint64_t rb = flip ? tile_transpose(ib) : ib;  // row-major form: byte r = row r
+        const S *src = vals + offsets[j];
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+            const int row = G == 1 ? i : t;
+            uint32_t byte = tile_byte(rb, row);
+            while (byte) {
+                const int c = __builtin_clz(byte) - 24;
+                byte &= ~(0x80u >> c);
+                const int p = 8 * row + c;
+                const U b = P::abs_bits(src[tile_rank(ib, flip ? transposed_pos(p) : p)]);
+                if (b <= P::kInf && b > m[i]) m[i] = b;
+            }
+        }
+    }
+    // segmented inclusive max over the lanes of one block-row (and, G = 8, of one tile row): they are G apart and contiguous
+    const int lane = lane_id();
+#pragma unroll
+    for (int d = G; d < kWave; d <<= 1) {
+        const uint32_t ob = __shfl_up(brow, d, kWave);
+        const bool same = lane >= d && ob == brow;
+#pragma unroll
+        for (int i = 0; i < R; i++) {
+            const U om = __shfl_up(m[i], d, kWave);
+            if (same && om > m[i]) m[i] = om;
+        }
+    }
+    const uint32_t nxt = __shfl_down(brow, G, kWave);
+    if (!live || (lane + G < kWave && nxt == brow)) return;  // a later lane of the wave carries this block-row on
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+        const int64_t row = (int64_t)brow * 8 + (G == 1 ? i : t);
+        if (m[i] && row < num_rows) atomic_max_bits(rowmax + row, m[i]);
+    }
+}
+
+// kept[j]: the bits of tile j's bitmap (A's layout) whose entries stay
+template <typename S, int G>
+__global__ __launch_bounds__(kThreads) void prune_mark_kernel(const uint64_t *__restrict__ keys, const uint64_t *__restrict__ bmps,
+                                                              const uint64_t *__restrict__ offsets, const S *__restrict__ vals, uint64_t nb,
+                                                              int transposed, int rule, double tol, int keep_diagonal,
+                                                              const typename PruneType<S>::R *__restrict__ rowmax, uint64_t *__restrict__ kept)
+{
+    using P = PruneType<S>;
+    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t j = gid / G;
+    const int t = (int)(gid % G);
+    const bool live = j < nb;
+    uint64_t keep = 0;
+    if (live) {
+        const uint64_t key = keys[j], ib = bmps[j];
+        const uint64_t mine = G == 1 ? ib : ib & byte_mask(t);
+        const S *src = vals + offsets[j] + (G == 1 ? 0 : tile_rank(ib, 8 * t));
+        const uint64_t row0 = (uint64_t)key_row(key) * 8;
+        uint64_t m = mine;
+        while (m) {
+            const int p = __builtin_clzll(m);
+            const uint64_t bit = 1ull << (63 - p);
+            m &= ~bit;
+            const double a = fabs(P::widen(*src++));
+            double thr = tol;
+            if (rule == BMSP_PRUNE_ROW_REL) thr = tol * (double)rowmax[row0 + (transposed ? (p & 7) : (p >> 3))];  // one IEEE multiply
+            if (!(a <= thr)) keep |= bit;  // NaN stays
+        }
+        if (keep_diagonal && key_row(key) == key_col(key)) keep |= mine & kTileDiagonal;
+    }
+    if (G == 8) {
+        keep |= __shfl_xor(keep, 1, kWave);
+        keep |= __shfl_xor(keep, 2, kWave);
+        keep |= __shfl_xor(keep, 4, kWave);
+    }
+    if (live && t == 0) kept[j] = keep;
+}
+
+// {tile kept (low 32 bits), kept values (high 32 bits)} of tile j; 0 at j == nb
+struct KeptIn {
+    const uint64_t *kept;
+    uint64_t nb;
+    __device__ uint64_t operator()(uint64_t j) const
+    {
+        if (j >= nb) return 0;
+        const uint64_t b = kept[j];
+        return (uint64_t)(b != 0) | (uint64_t)popc64(b) << 32;
+    }
+};
+
+struct KeptOut {
+    uint64_t *pos;  // nb + 1: {output slot, output value offset} of tile j; the totals at nb
+    uint64_t nb;
+    uint64_t *total;  // host scalar
+    __device__ void operator()(uint64_t j, uint64_t ex) const
+    {
+        pos[j] = ex;
+        if (j == nb) *total = ex;
+    }
+};
+
+// A's tiles [0, nb): a kept tile goes to its slot with its kept values; index nb writes the terminal offset
+template <typename T, int G>
+__global__ __launch_bounds__(kThreads) void prune_place_kernel(const uint64_t *__restrict__ a_keys, const uint64_t *__restrict__ a_bmps,
+                                                               const uint64_t *__restrict__ a_off, const T *__restrict__ a_vals,
+                                                               const uint64_t *__restrict__ kept, const uint64_t *__restrict__ pos, uint64_t nb,
+                                                               int flip, uint64_t *__restrict__ o_keys, uint64_t *__restrict__ o_bmps,
+                                                               uint64_t *__restrict__ o_off, T *__restrict__ o_vals)
+{
+    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+    const uint64_t j = gid / G;
+    const int t = (int)(gid % G);
+    if (j > nb) return;
+    const uint64_t w = pos[j];
+    const uint64_t c = (uint32_t)w, off = w >> 32;
+    if (j == nb) {
+        if (t == 0) o_off[c] = off;
+        return;
+    }
+    const uint64_t kb = kept[j];
+    if (!kb) return;
+    const uint64_t ib = a_bmps[j];
+    const uint64_t ob = flip ? tile_transpose(kb) : kb;
+    if (t == 0) {
+        o_keys[c] = a_keys[j];
+        o_bmps[c] = ob;
+        o_off[c] = off;
+    }
+    uint64_t m = G == 1 ? ob : ob & byte_mask(t);
+    T *dst = o_vals + off + (G == 1 ? 0 : tile_rank(ob, 8 * t));
+    const T *src = a_vals + a_off[j];
+    while (m) {
+        const int p = __builtin_clzll(m);
+        m &= ~(1ull << (63 - p));
+        *dst++ = src[tile_rank(ib, flip ? transposed_pos(p) : p)];
+    }
+}
+
+// lanes per tile from the mean tile fill, the rule of the transpose's and the sum's value passes: a lane per tile below 6 values, eight
+// from there.  BMSP_PRUNE_LANES = 1 / 8 forces one (measurement and test switch, read per call).
+int prune_group(int64_t nnz, int64_t nb)
+{
+    if (const char *e = getenv("BMSP_PRUNE_LANES")) {
+        const int g = atoi(e);
+        if (g == 1 || g == 8) return g;
+    }
+    return nb == 0 || nnz < 6 * nb ? 1 : 8;
+}
+
+template <typename S>
+void launch_row_absmax(int g, const bmsp_matrix_s *A, int64_t num_rows, void *rowmax, hipStream_t st)
+{
+    using U = typename PruneType<S>::U;
+    const uint64_t nb = (uint64_t)A->block_num;
+    if (g == 8)
+        hipLaunchKernelGGL((row_absmax_kernel<S, 8>), grid_for(nb * 8), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets, (const S *)A->values,
+                           nb, A->transposed, num_rows, (U *)rowmax);
+    else
+        hipLaunchKernelGGL((row_absmax_kernel<S, 1>), grid_for(nb), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets, (const S *)A->values, nb,
+                           A->transposed, num_rows, (U *)rowmax);
+    BMSP_CHECK_LAUNCH();
+}
+
+template <typename S>
+void launch_mark(int g, const bmsp_matrix_s *A, int rule, double tol, int flags, const void *rowmax, uint64_t *kept, hipStream_t st)
+{
+    using R = typename PruneType<S>::R;
+    const uint64_t nb = (uint64_t)A->block_num;
+    const int kd = flags & BMSP_PRUNE_KEEP_DIAGONAL;
+    if (g == 8)
+        hipLaunchKernelGGL((prune_mark_kernel<S, 8>), grid_for(nb * 8), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets, (const S *)A->values,
+                           nb, A->transposed, rule, tol, kd, (const R *)rowmax, kept);
+    else
+        hipLaunchKernelGGL((prune_mark_kernel<S, 1>), grid_for(nb), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets, (const S *)A->values, nb,
+                           A->transposed, rule, tol, kd, (const R *)rowmax, kept);
+    BMSP_CHECK_LAUNCH();
+}
+
+template <typename T>
+void launch_place(int g, const bmsp_matrix_s *A, const uint64_t *kept, const uint64_t *pos, bmsp_matrix_s *out, hipStream_t st)
+{
+    const uint64_t nb = (uint64_t)A->block_num;
+    const int flip = A->transposed != out->transposed;
+    if (g == 8)
+        hipLaunchKernelGGL((prune_place_kernel<T, 8>), grid_for((nb + 1) * 8), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets,
+                           (const T *)A->values, kept, pos, nb, flip, out->keys, out->bmps, out->offsets, (T *)out->values);
+    else
+        hipLaunchKernelGGL((prune_place_kernel<T, 1>), grid_for(nb + 1), dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets,
+                           (const T *)A->values, kept, pos, nb, flip, out->keys, out->bmps, out->offsets, (T *)out->values);
+    BMSP_CHECK_LAUNCH();
+}
+
+#define BMSP_PRUNE_DISPATCH(dtype, fn, ...)                          \
+    do {                                                             \
+        if ((dtype) == BMSP_F16) fn<uint16_t>(__VA_ARGS__);          \
+        else if ((dtype) == BMSP_F32) fn<float>(__VA_ARGS__);        \
+        else fn<double>(__VA_ARGS__);                                \
+    } while (0)
+
+void check_source(const bmsp_matrix_s *A, const char *what)
+{
+    if (A->view_block_begin || A->view_values_end) fail(BMSP_ERR_INVALID, "%s: matrix A is a row-panel view; use the parent", what);
+    // slots and kept values are counted in the two 32-bit halves of one scan word
+    if (A->block_num >= 0xffffffffll) fail(BMSP_ERR_LIMIT, "%s: %lld tiles exceed the 32-bit slot count", what, (long long)A->block_num);
+    if (A->nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "%s: nnz %lld exceeds the 32-bit value count", what, (long long)A->nnz);
+}
+
+// zeroes `rowmax` (`entries` of A's row-maximum type) and fills its first num_rows entries
+void compute_row_absmax(const bmsp_matrix_s *A, void *rowmax, int64_t entries, hipStream_t st)
+{
+    const size_t es = A->dtype == BMSP_F64 ? 8 : 4;
+    if (entries == 0) return;
+    BMSP_HIP(hipMemsetAsync(rowmax, 0, es * (size_t)entries, st));
+    if (A->block_num == 0 || A->nnz == 0) return;
+    const int g = prune_group(A->nnz, A->block_num);
+    BMSP_PRUNE_DISPATCH(A->dtype, launch_row_absmax, g, A, (int64_t)A->num_rows, rowmax, st);
+}
+
+}  // namespace
+
+void prune_check_args(int rule, double tol, int flags, int out_transposed)
+{
+    if (rule != BMSP_PRUNE_ABS && rule != BMSP_PRUNE_ROW_REL)
+        fail(BMSP_ERR_INVALID, "rule must be BMSP_PRUNE_ABS (0) or BMSP_PRUNE_ROW_REL (1) (got %d)", rule);
+    if (!(tol >= 0.0)) fail(BMSP_ERR_INVALID, "tol must be >= 0 and not NaN (got %g)", tol);
+    if (rule == BMSP_PRUNE_ROW_REL && std::isinf(tol)) fail(BMSP_ERR_INVALID, "tol must be finite under BMSP_PRUNE_ROW_REL (Inf * 0 is NaN for an empty row)");
+    if (flags & ~BMSP_PRUNE_KEEP_DIAGONAL) fail(BMSP_ERR_INVALID, "flags has unknown bits (got 0x%x)", (unsigned)flags);
+    if (out_transposed != 0 && out_transposed != 1) fail(BMSP_ERR_INVALID, "out_transposed must be 0 or 1 (got %d)", out_transposed);
+}
+
+void row_absmax(bmsp_matrix_s *A, void *d_rowmax, hipStream_t st)
+{
+    check_source(A, "row_absmax");
+    compute_row_absmax(A, d_rowmax, A->num_rows, st);
+}
+
+// *out (when out is not null) = A without the entries the rule drops, tiles in layout out_transposed; *stats (when not null) the counts
+void prune_matrix(bmsp_matrix_s *A, int rule, double tol, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
+                  bmsp_prune_stats *stats)
+{
+    prune_check_args(rule, tol, flags, out_transposed);
+    if (!out && !stats) fail(BMSP_ERR_INVALID, "prune: out and stats are both null");
+    check_source(A, "prune");
+    const uint64_t nb = (uint64_t)A->block_num;
+    const int g = prune_group(A->nnz, A->block_num);
+    DevBuf<uint64_t> kept(nb), pos(nb + 1);  // temporaries: back to the pool after the synchronisation at the end
+    DevBuf<uint64_t> rowmax;                 // (holds floats for F32 / F16)
+    if (rule == BMSP_PRUNE_ROW_REL) {
+        const int64_t padded = A->num_block_rows() * 8;  // every row a key can name
+        rowmax.alloc((size_t)padded);
+        compute_row_absmax(A, rowmax.p, padded, st);
+    }
+    if (nb) BMSP_PRUNE_DISPATCH(A->dtype, launch_mark, g, A, rule, tol, flags, rowmax.p, kept.p, st);
+    HostScalar<uint64_t> total;
+    device_exclusive_scan<uint64_t>(KeptIn{kept.p, nb}, KeptOut{pos.p, nb, total.dev()}, nb + 1, st);
+    const uint64_t t = total.wait(st);
+    const uint64_t nc = (uint32_t)t, nnz_out = t >> 32;
+    if (stats) {
+        stats->nnz_in = A->nnz; stats->blocks_in = A->block_num;
+        stats->nnz_out = (int64_t)nnz_out; stats->blocks_out = (int64_t)nc;
+    }
+    if (!out) {
+        BMSP_HIP(hipStreamSynchronize(st));  // the temporaries go back to the pool
+        return;
+    }
+    std::unique_ptr<bmsp_matrix_s, void (*)(bmsp_matrix_s *)> m(new bmsp_matrix_s(), free_matrix);
+    m->num_rows = A->num_rows; m->num_cols = A->num_cols; m->dtype = A->dtype; m->transposed = out_transposed;
+    m->block_num = (int64_t)nc;
+    m->nnz = (int64_t)nnz_out;
+    m->keys = (uint64_t *)pool_alloc(8 * (nc ? nc : 1));
+    m->bmps = (uint64_t *)pool_alloc(8 * (nc ? nc : 1));
+    m->offsets = (uint64_t *)pool_alloc(8 * (nc + 1));
+    m->values = pool_alloc(dtype_size(m->dtype) * (size_t)(nnz_out ? nnz_out : 1));
+    // the lane group of the move follows what is left of the tiles
+    const int gp = prune_group(m->nnz, m->block_num);
+    const size_t es = dtype_size(m->dtype);
+    if (es == 2) launch_place<uint16_t>(gp, A, kept.p, pos.p, m.get(), st);
+    else if (es == 4) launch_place<uint32_t>(gp, A, kept.p, pos.p, m.get(), st);
+    else launch_place<uint64_t>(gp, A, kept.p, pos.p, m.get(), st);
+    ensure_rowptr(m.get(), st);
+    BMSP_HIP(hipStreamSynchronize(st));
+    *out = m.release();
+}
+
+}  // namespace bmsp
+
+BMSP_DEFINE_WARM(prune)

@@ -19,6 +19,9 @@ NP_DTYPE = {F32: np.float32, F16: np.float16, F64: np.float64}
 OUT_DTYPE = {F32: np.float32, F16: np.float32, F64: np.float64}
 SORT_AUTO, SORT_SEGMENTED, SORT_GLOBAL = 0, 1, 2
 SPMV_DEFAULT, SPMV_BATCHED = 0, 1
+PRUNE_ABS, PRUNE_ROW_REL = 0, 1
+PRUNE_KEEP_DIAGONAL = 1
+_PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
 # every symbol include/bmsp.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = [
@@ -28,6 +31,7 @@ SYMBOLS = [
     "bmsp_matrix_from_mtx", "bmsp_matrix_from_coo", "bmsp_matrix_from_coo_device", "bmsp_matrix_from_arrays",
     "bmsp_matrix_save", "bmsp_matrix_load", "bmsp_matrix_free", "bmsp_matrix_prepare", "bmsp_matrix_invalidate", "bmsp_matrix_info", "bmsp_matrix_arrays", "bmsp_matrix_block_row_ptr",
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
+    "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmm", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
@@ -52,6 +56,13 @@ class SpgemmStats(C.Structure):
                                            "sort_path", "mac_kernel", "mac_variant", "sort_long")}
         d["t_us"] = list(self.t_us)
         return d
+
+
+class PruneStats(C.Structure):
+    _fields_ = [("nnz_in", C.c_int64), ("nnz_out", C.c_int64), ("blocks_in", C.c_int64), ("blocks_out", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ShardStats(C.Structure):
@@ -107,6 +118,8 @@ def lib():
         L.bmsp_matrix_copy_values.argtypes = [vp, vp, vp]
         L.bmsp_matrix_add.argtypes = [C.c_double, vp, C.c_double, vp, i, vp, p(vp)]
         L.bmsp_matrix_add_values.argtypes = [C.c_double, vp, C.c_double, vp, vp, vp]
+        L.bmsp_matrix_prune.argtypes = [vp, i, C.c_double, i, i, vp, p(vp), p(PruneStats)]
+        L.bmsp_matrix_row_absmax.argtypes = [vp, vp, vp]
         L.bmsp_matrix_to_coo_host.argtypes = [vp, vp, vp, vp]
         L.bmsp_matrix_to_coo_device.argtypes = [vp, vp, vp, vp, vp]
         L.bmsp_matrix_to_csr_device.argtypes = [vp, vp, vp, vp, vp]
@@ -360,6 +373,10 @@ class BmSpMatrix:
         check(lib().bmsp_matrix_convert_layout(self.h, int(bool(transposed)), stream, C.byref(h)))
         return BmSpMatrix(h.value)
 
+    def prune(self, tol=0.0, rule="abs", keep_diagonal=False, transposed=None, stream=None):
+        """(this matrix without the entries the rule drops, stats dict): pybmsp.prune"""
+        return prune(self, tol, rule, keep_diagonal, transposed, stream)
+
     def copy_values_from(self, src, stream=None):
         """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
         check(lib().bmsp_matrix_copy_values(src.h, self.h, stream))
@@ -438,6 +455,39 @@ def add_values(Cm, A, B, alpha=1.0, beta=1.0, stream=None):
     """re-computes the values of Cm = add(A, B, ...) from A's and B's current values (bmsp_matrix_add_values)."""
     check(lib().bmsp_matrix_add_values(float(alpha), A.h, float(beta), B.h, Cm.h, stream))
     return Cm
+
+
+def _prune_rule(rule):
+    if rule not in _PRUNE_RULES:
+        raise ValueError("rule must be 'abs' or 'row_rel' (got %r)" % (rule,))
+    return _PRUNE_RULES[rule]
+
+
+def prune(A, tol=0.0, rule="abs", keep_diagonal=False, transposed=None, stream=None):
+    """A without the stored entries with |v| <= tol (rule "abs") or |v| <= tol * rowmax(row) (rule "row_rel") as a new matrix
+    (bmsp_matrix_prune), its tiles in layout `transposed` (None: A's layout); returns (matrix, {"nnz_in", "nnz_out", "blocks_in",
+    "blocks_out"}).  keep_diagonal: entries with row == col always stay."""
+    lay = A.info()["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    st = PruneStats()
+    check(lib().bmsp_matrix_prune(A.h, _prune_rule(rule), float(tol), PRUNE_KEEP_DIAGONAL if keep_diagonal else 0, lay, stream, C.byref(h),
+                                  C.byref(st)))
+    return BmSpMatrix(h.value), st.as_dict()
+
+
+def prune_count(A, tol=0.0, rule="abs", keep_diagonal=False, stream=None):
+    """the stats prune() would return, without making the output (the marking passes only)."""
+    st = PruneStats()
+    check(lib().bmsp_matrix_prune(A.h, _prune_rule(rule), float(tol), PRUNE_KEEP_DIAGONAL if keep_diagonal else 0, 0, stream, None, C.byref(st)))
+    return st.as_dict()
+
+
+def row_absmax(A, stream=None):
+    """max |v| over the stored, non-NaN entries of every row (0 for a row with none) as a DeviceArray (float32; float64 for F64)."""
+    i = A.info()
+    out = DeviceArray(i["num_rows"], OUT_DTYPE[i["dtype"]])
+    check(lib().bmsp_matrix_row_absmax(A.h, out.ptr, stream))
+    return out
 
 
 # bmSparse_SpMV(A, v, u, batched)

@@ -210,6 +210,17 @@ public:
         return out;
     }
 
+    /* this matrix without the stored entries the rule drops (bmsp_matrix_prune): |v| <= tol under BMSP_PRUNE_ABS, |v| <= tol * rowmax
+     * under BMSP_PRUNE_ROW_REL; tol = 0 drops the stored zeros a product or a sum leaves behind */
+    bmSpMatrix<valueType> prune(double tol, int rule = BMSP_PRUNE_ABS, bool keep_diagonal = false, bool transposed_layout = false) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_prune(h_, rule, tol, keep_diagonal ? BMSP_PRUNE_KEEP_DIAGONAL : 0, transposed_layout ? 1 : 0, nullptr, &t, nullptr));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+
     /* src/bmSpMatrix.cu:320-363 */
     void generate_coo()
     {
@@ -300,6 +311,17 @@ template <class valueType>
 inline void bmSparse_add_values(double alpha, bmSpMatrix<valueType> &A, double beta, bmSpMatrix<valueType> &B, bmSpMatrix<valueType> &C)
 {
     bmsp::check(bmsp_matrix_add_values(alpha, A.handle(), beta, B.handle(), C.handle(), nullptr));
+}
+
+/* C = A without the stored entries the rule drops (bmsp_matrix_prune), C's tiles column-major when transposed_layout; stats (optional)
+ * receives the entry and tile counts before and after. */
+template <class valueType>
+inline void bmSparse_prune(bmSpMatrix<valueType> &A, bmSpMatrix<valueType> &C, double tol, int rule = BMSP_PRUNE_ABS, bool keep_diagonal = false,
+                           bool transposed_layout = false, bmsp_prune_stats *stats = nullptr)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_matrix_prune(A.handle(), rule, tol, keep_diagonal ? BMSP_PRUNE_KEEP_DIAGONAL : 0, transposed_layout ? 1 : 0, nullptr, &c, stats));
+    C.reset(c);
 }
 
 /* The same product sharded over one process per GPU (bmsp_spgemm_sharded): every rank passes the same A and B, multiplies

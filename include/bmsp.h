@@ -151,6 +151,35 @@ int bmsp_matrix_copy_values(bmsp_matrix_t A, bmsp_matrix_t out, void *stream);
  *       does; asynchronous on `stream` unless C holds such caches (dropping them synchronises the device). */
 int bmsp_matrix_add(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, int out_transposed, void *stream, bmsp_matrix_t *C);
 int bmsp_matrix_add_values(double alpha, bmsp_matrix_t A, double beta, bmsp_matrix_t B, bmsp_matrix_t C, void *stream);
+/* Pruning: out = A without the stored entries a rule drops, on the device (no COO round trip).  The library otherwise keeps every
+ * coordinate it has stored (a product's structure is symbolic, A + (-A) keeps A's structure); this is the call that shrinks a matrix.
+ *   Rules: BMSP_PRUNE_ABS drops an entry iff |v| <= tol; BMSP_PRUNE_ROW_REL iff |v| <= tol * rowmax(row of the entry).  With
+ *       BMSP_PRUNE_KEEP_DIAGONAL in `flags` an entry with row == col is never dropped.
+ *   Comparison: exact, in double.  The stored value (F16 / F32 / F64) is widened exactly and `tol` is used as given (not rounded to the
+ *       storage type); ROW_REL forms tol * rowmax as one IEEE double multiply, then compares.  There is no other arithmetic, so the result
+ *       is a pure function of the bits of A and of tol.  tol = 0 under ABS drops exactly the entries equal to +0 or -0: subnormals are
+ *       not zero and are kept.  NaN is never dropped by either rule (the comparison is false); +-Inf only by ABS with tol = +Inf.
+ *   rowmax(i) = max of |v| over the stored, non-NaN entries of matrix row i (matrix coordinates, whatever the tile layout); 0 for a row
+ *       with none.  bmsp_matrix_row_absmax writes exactly this to d_rowmax: num_rows entries, float for F32 / F16 and double for F64
+ *       (the convention of bmsp_spmv's u); asynchronous on `stream`; A is not modified.
+ *   Output: a fresh pool-owned handle of A's shape and dtype, tiles in layout `out_transposed` (0 row-major, 1 column-major; A may have
+ *       either).  Its four arrays equal, bit for bit, what the builders make from the COO of A's kept entries in that layout: tiles that
+ *       lose every entry disappear, offsets hold block_num+1 entries, kept values move as raw bits (-0 under a rule that keeps it, NaN
+ *       payloads and subnormals survive).  An output with 0 tiles is a valid matrix.
+ *   Count only: out == NULL with stats != NULL runs the marking passes alone and fills *stats (what a caller uses to pick a tolerance).
+ *       With out != NULL, stats may be NULL.
+ *   A and its caches are never modified.  bmsp_matrix_prune runs on `stream` and synchronises it before it returns (the kept counts are
+ *   read back).  Refused with BMSP_ERR_INVALID, the message naming the argument: rule not 0 / 1; tol negative or NaN; ROW_REL with
+ *   tol = +Inf (Inf * 0 is NaN for an empty or all-zero row); flags with unknown bits; out_transposed not 0 / 1; out and stats both NULL;
+ *   null A; null d_rowmax; row-panel views.  The scalar arguments are checked before the handles.  BMSP_ERR_LIMIT: A holds 2^32 - 1
+ *   tiles or more, or 2^32 values or more (kept tiles and kept values are counted in the two 32-bit halves of one scan word). */
+#define BMSP_PRUNE_ABS      0   /* drop an entry iff |v| <= tol                                  */
+#define BMSP_PRUNE_ROW_REL  1   /* drop an entry iff |v| <= tol * rowmax(row of the entry)       */
+#define BMSP_PRUNE_KEEP_DIAGONAL 1  /* flags bit 0: an entry with row == col is never dropped    */
+typedef struct { int64_t nnz_in, nnz_out, blocks_in, blocks_out; } bmsp_prune_stats;
+int bmsp_matrix_prune(bmsp_matrix_t A, int rule, double tol, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
+                      bmsp_prune_stats *stats);
+int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream);
 /* dense block-row pointer (num_block_rows+1 uint32 entries) the operators use; built once and cached
  * (the reference rebuilds a compressed one on every call, src/bmSparse_SPMV.cu:199-206). */
 int bmsp_matrix_block_row_ptr(bmsp_matrix_t m, const uint32_t **d_rowptr, int64_t *num_block_rows);
