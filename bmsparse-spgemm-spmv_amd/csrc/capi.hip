@@ -405,6 +405,46 @@ int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream)
     BMSP_API_END
 }
 
+int bmsp_matrix_diagonal(bmsp_matrix_t A, void *d_diag, void *stream)
+{
+    BMSP_API_BEGIN
+    need(A, "matrix A"); need(d_diag, "d_diag");
+    load_kernels();
+    matrix_diagonal(A, d_diag, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_from_diagonal(int num_rows, int num_cols, const void *d_diag, bmsp_dtype dtype, int transposed, void *stream,
+                              bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    from_diagonal_check_args(num_rows, num_cols, d_diag, dtype, transposed);
+    need(out, "out");
+    load_kernels();
+    *out = matrix_from_diagonal(num_rows, num_cols, d_diag, dtype, transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_scale(bmsp_matrix_t A, const void *d_left, const void *d_right, int flags, int out_transposed, void *stream,
+                      bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    scale_check_args(d_left, d_right, flags, out_transposed);
+    need(A, "matrix A"); need(out, "out");
+    load_kernels();
+    *out = scale_matrix(A, d_left, d_right, flags, out_transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_matrix_scale_values(bmsp_matrix_t A, const void *d_left, const void *d_right, int flags, bmsp_matrix_t out, void *stream)
+{
+    BMSP_API_BEGIN
+    scale_check_args(d_left, d_right, flags, 0);
+    need(A, "matrix A"); need(out, "matrix out");
+    scale_values_into(A, d_left, d_right, flags, out, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_matrix_info(bmsp_matrix_t m, int *num_rows, int *num_cols, int64_t *nnz, int64_t *block_num, bmsp_dtype *dtype, int *transposed)
 {
     BMSP_API_BEGIN

@@ -71,7 +71,7 @@ struct bmsp_matrix_s {
     // a product remembers which operand STRUCTURES it was formed from (struct_hash of A and B; 0 = not stamped: a view, adopted arrays): the
     // fast paths of bmsp_spgemm_numeric trust C only when the stamps match the operands it is given
     uint64_t sp_a_hash = 0, sp_b_hash = 0;
-    // made by bmsp_matrix_transpose / bmsp_matrix_convert_layout: the source's uid (0 = neither), the source tile of every tile (the sort's
+    // made by bmsp_matrix_transpose / bmsp_matrix_convert_layout / bmsp_matrix_scale: the source's uid (0 = neither), the source tile of every tile (the sort's
     // payload; null = the source's tile order) and whether values are permuted inside each tile -- what bmsp_matrix_copy_values replays
     uint64_t tp_src_uid = 0;
     uint32_t *tp_map = nullptr;
@@ -198,6 +198,14 @@ void prune_check_args(int rule, double tol, int flags, int out_transposed);
 void prune_matrix(bmsp_matrix_s *A, int rule, double tol, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
                   bmsp_prune_stats *stats);
 void row_absmax(bmsp_matrix_s *A, void *d_rowmax, hipStream_t st);
+// diag.hip: the diagonal as a vector, a diagonal matrix from a vector, out = diag(l) * A * diag(r) as a new matrix (tiles in layout
+// out_transposed) or into A itself / a matrix made from A by scale_matrix or a layout conversion
+void scale_check_args(const void *d_left, const void *d_right, int flags, int out_transposed);
+void from_diagonal_check_args(int num_rows, int num_cols, const void *d_diag, bmsp_dtype dtype, int transposed);
+void matrix_diagonal(bmsp_matrix_s *A, void *d_diag, hipStream_t st);
+bmsp_matrix_s *matrix_from_diagonal(int num_rows, int num_cols, const void *d_diag, bmsp_dtype dtype, int transposed, hipStream_t st);
+bmsp_matrix_s *scale_matrix(bmsp_matrix_s *A, const void *d_left, const void *d_right, int flags, int out_transposed, hipStream_t st);
+void scale_values_into(bmsp_matrix_s *A, const void *d_left, const void *d_right, int flags, bmsp_matrix_s *out, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

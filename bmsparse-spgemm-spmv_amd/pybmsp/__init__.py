@@ -21,6 +21,7 @@ SORT_AUTO, SORT_SEGMENTED, SORT_GLOBAL = 0, 1, 2
 SPMV_DEFAULT, SPMV_BATCHED = 0, 1
 PRUNE_ABS, PRUNE_ROW_REL = 0, 1
 PRUNE_KEEP_DIAGONAL = 1
+SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
 # every symbol include/bmsp.h declares (checked by tests/test_abi.py against the header text)
@@ -32,6 +33,7 @@ SYMBOLS = [
     "bmsp_matrix_save", "bmsp_matrix_load", "bmsp_matrix_free", "bmsp_matrix_prepare", "bmsp_matrix_invalidate", "bmsp_matrix_info", "bmsp_matrix_arrays", "bmsp_matrix_block_row_ptr",
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
+    "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
     "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmm", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
@@ -120,6 +122,10 @@ def lib():
         L.bmsp_matrix_add_values.argtypes = [C.c_double, vp, C.c_double, vp, vp, vp]
         L.bmsp_matrix_prune.argtypes = [vp, i, C.c_double, i, i, vp, p(vp), p(PruneStats)]
         L.bmsp_matrix_row_absmax.argtypes = [vp, vp, vp]
+        L.bmsp_matrix_diagonal.argtypes = [vp, vp, vp]
+        L.bmsp_matrix_from_diagonal.argtypes = [i, i, vp, i, i, vp, p(vp)]
+        L.bmsp_matrix_scale.argtypes = [vp, vp, vp, i, i, vp, p(vp)]
+        L.bmsp_matrix_scale_values.argtypes = [vp, vp, vp, i, vp, vp]
         L.bmsp_matrix_to_coo_host.argtypes = [vp, vp, vp, vp]
         L.bmsp_matrix_to_coo_device.argtypes = [vp, vp, vp, vp, vp]
         L.bmsp_matrix_to_csr_device.argtypes = [vp, vp, vp, vp, vp]
@@ -377,6 +383,23 @@ class BmSpMatrix:
         """(this matrix without the entries the rule drops, stats dict): pybmsp.prune"""
         return prune(self, tol, rule, keep_diagonal, transposed, stream)
 
+    def diagonal(self, stream=None):
+        """the diagonal as a DeviceArray of min(num_rows, num_cols) entries, +0 where (i, i) is not stored: pybmsp.diagonal"""
+        return diagonal(self, stream)
+
+    def scale(self, left=None, right=None, div_left=False, div_right=False, transposed=None, stream=None):
+        """diag(left) * this * diag(right) as a new matrix: pybmsp.scale"""
+        return scale(self, left, right, div_left, div_right, transposed, stream)
+
+    def scale_(self, left=None, right=None, div_left=False, div_right=False, stream=None):
+        """the same into this matrix's own values (bmsp_matrix_scale_values with out == A)"""
+        return scale_values(self, self, left, right, div_left, div_right, stream)
+
+    @staticmethod
+    def from_diagonal(d, num_rows=None, num_cols=None, dtype=F32, transposed=False, stream=None):
+        """the matrix with d[i] stored at every (i, i): pybmsp.from_diagonal"""
+        return from_diagonal(d, num_rows, num_cols, dtype, transposed, stream)
+
     def copy_values_from(self, src, stream=None):
         """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
         check(lib().bmsp_matrix_copy_values(src.h, self.h, stream))
@@ -487,6 +510,55 @@ def row_absmax(A, stream=None):
     i = A.info()
     out = DeviceArray(i["num_rows"], OUT_DTYPE[i["dtype"]])
     check(lib().bmsp_matrix_row_absmax(A.h, out.ptr, stream))
+    return out
+
+
+def diagonal(A, stream=None):
+    """the stored value at every (i, i), i < min(num_rows, num_cols), +0 where none is stored, as a DeviceArray (float32; float64 for
+    F64) (bmsp_matrix_diagonal; asynchronous on `stream`)."""
+    i = A.info()
+    out = DeviceArray(min(i["num_rows"], i["num_cols"]), OUT_DTYPE[i["dtype"]])
+    check(lib().bmsp_matrix_diagonal(A.h, out.ptr, stream))
+    return out
+
+
+def from_diagonal(d, num_rows=None, num_cols=None, dtype=F32, transposed=False, stream=None):
+    """the num_rows x num_cols matrix (default: d.n x d.n) with d[i] stored at every (i, i), zeros included (bmsp_matrix_from_diagonal).
+    d: DeviceArray of at least min(num_rows, num_cols) entries, float32 (float64 for F64)."""
+    nr = d.n if num_rows is None else int(num_rows)
+    nc = d.n if num_cols is None else int(num_cols)
+    if d.dtype != np.dtype(OUT_DTYPE[dtype]) or d.n < min(nr, nc):
+        raise ValueError("d must hold at least min(num_rows, num_cols) entries of %s" % np.dtype(OUT_DTYPE[dtype]).name)
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_from_diagonal(nr, nc, d.ptr, dtype, int(bool(transposed)), stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def _scale_args(A, left, right, div_left, div_right):
+    i = A.info()
+    for name, v, n in (("left", left, i["num_rows"]), ("right", right, i["num_cols"])):
+        if v is not None and (v.dtype != np.dtype(OUT_DTYPE[i["dtype"]]) or v.n < n):
+            raise ValueError("%s must hold %d entries of %s" % (name, n, np.dtype(OUT_DTYPE[i["dtype"]]).name))
+    flags = (SCALE_DIV_LEFT if div_left else 0) | (SCALE_DIV_RIGHT if div_right else 0)
+    return i, None if left is None else left.ptr, None if right is None else right.ptr, flags
+
+
+def scale(A, left=None, right=None, div_left=False, div_right=False, transposed=None, stream=None):
+    """diag(left) * A * diag(right) as a new matrix with A's structure (bmsp_matrix_scale), its tiles in layout `transposed` (None: A's
+    layout).  left / right: DeviceArrays of num_rows / num_cols entries (float32; float64 for F64); None skips that side; div_left /
+    div_right divide by that side instead.  Asynchronous on `stream`."""
+    i, lp, rp, flags = _scale_args(A, left, right, div_left, div_right)
+    lay = i["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_scale(A.h, lp, rp, flags, lay, stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def scale_values(out, A, left=None, right=None, div_left=False, div_right=False, stream=None):
+    """the values of diag(left) * A * diag(right) into `out`: A itself (in place) or a matrix made from A by scale() / with_layout()
+    (bmsp_matrix_scale_values)."""
+    _, lp, rp, flags = _scale_args(A, left, right, div_left, div_right)
+    check(lib().bmsp_matrix_scale_values(A.h, lp, rp, flags, out.h, stream))
     return out
 
 

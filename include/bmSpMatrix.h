@@ -43,6 +43,9 @@ template <> struct dtype_of<double> { static const bmsp_dtype value = BMSP_F64; 
 #ifndef BMSP_NO_HALF_TYPE
 template <> struct dtype_of<half> { static const bmsp_dtype value = BMSP_F16; };
 #endif
+/* element type of the vectors that go with a matrix (SpMV results, row maxima, diagonals, scaling factors): float, double for double */
+template <class T> struct vector_of { typedef float type; };
+template <> struct vector_of<double> { typedef double type; };
 
 /* The subset of thrust::device_vector the reference's code uses: size/data/begin/end/swap/clear/shrink_to_fit,
  * construction from a host vector, copy back to the host.  Owns pool memory unless it is a view. */
@@ -221,6 +224,33 @@ public:
         return out;
     }
 
+    /* the diagonal as a device vector of min(num_rows, num_cols) entries, +0 where (i, i) is not stored (bmsp_matrix_diagonal) */
+    bmsp::device_vector<typename bmsp::vector_of<valueType>::type> diagonal() const
+    {
+        bmsp::device_vector<typename bmsp::vector_of<valueType>::type> d((size_t)(num_rows < num_cols ? num_rows : num_cols));
+        bmsp::check(bmsp_matrix_diagonal(h_, d.data(), nullptr));
+        bmsp::check(bmsp_synchronize());
+        return d;
+    }
+    /* diag(left) * this * diag(right) as a new matrix (bmsp_matrix_scale): device vectors of num_rows / num_cols entries, a null one
+     * skips its side; flags = BMSP_SCALE_DIV_LEFT | BMSP_SCALE_DIV_RIGHT divides by that side instead */
+    bmSpMatrix<valueType> scale(const typename bmsp::vector_of<valueType>::type *left, const typename bmsp::vector_of<valueType>::type *right,
+                                int flags = 0, bool transposed_layout = false) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_scale(h_, left, right, flags, transposed_layout ? 1 : 0, nullptr, &t));
+        bmsp::check(bmsp_synchronize());
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+    /* the same into this matrix's own values (bmsp_matrix_scale_values with out == A) */
+    void scale_inplace(const typename bmsp::vector_of<valueType>::type *left, const typename bmsp::vector_of<valueType>::type *right, int flags = 0)
+    {
+        bmsp::check(bmsp_matrix_scale_values(h_, left, right, flags, h_, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+
     /* src/bmSpMatrix.cu:320-363 */
     void generate_coo()
     {
@@ -322,6 +352,31 @@ inline void bmSparse_prune(bmSpMatrix<valueType> &A, bmSpMatrix<valueType> &C, d
     bmsp_matrix_t c = nullptr;
     bmsp::check(bmsp_matrix_prune(A.handle(), rule, tol, keep_diagonal ? BMSP_PRUNE_KEEP_DIAGONAL : 0, transposed_layout ? 1 : 0, nullptr, &c, stats));
     C.reset(c);
+}
+
+/* Diagonal operations (bmsp_matrix_diagonal / _from_diagonal / _scale): d = diag(A) as a device vector (resized to min(num_rows,
+ * num_cols)); C = the num_rows x num_cols matrix with d[i] at every (i, i); C = diag(left) * A * diag(right), a null side skipped. */
+template <class valueType>
+inline void bmSparse_diagonal(bmSpMatrix<valueType> &A, bmsp::device_vector<typename bmsp::vector_of<valueType>::type> &d)
+{
+    d = A.diagonal();
+}
+template <class valueType>
+inline void bmSparse_from_diagonal(const bmsp::device_vector<typename bmsp::vector_of<valueType>::type> &d, bmSpMatrix<valueType> &C, int num_rows = -1,
+                                   int num_cols = -1, bool transposed_layout = false)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_matrix_from_diagonal(num_rows < 0 ? (int)d.size() : num_rows, num_cols < 0 ? (int)d.size() : num_cols, d.data(),
+                                          bmsp::dtype_of<valueType>::value, transposed_layout ? 1 : 0, nullptr, &c));
+    bmsp::check(bmsp_synchronize());
+    C.reset(c);
+}
+template <class valueType>
+inline void bmSparse_scale(bmSpMatrix<valueType> &A, const typename bmsp::vector_of<valueType>::type *left,
+                           const typename bmsp::vector_of<valueType>::type *right, bmSpMatrix<valueType> &C, int flags = 0,
+                           bool transposed_layout = false)
+{
+    C = A.scale(left, right, flags, transposed_layout);
 }
 
 /* The same product sharded over one process per GPU (bmsp_spgemm_sharded): every rank passes the same A and B, multiplies

@@ -180,6 +180,50 @@ typedef struct { int64_t nnz_in, nnz_out, blocks_in, blocks_out; } bmsp_prune_st
 int bmsp_matrix_prune(bmsp_matrix_t A, int rule, double tol, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
                       bmsp_prune_stats *stats);
 int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream);
+/* Diagonal operations: what connects a device VECTOR to a matrix besides bmsp_spmv, on the device (no COO round trip).  Nothing in the
+ * reference is replaced: it has no diagonal, scaling or addition entry point (include/bmSpMatrix.h:20-40 declares the builders,
+ * generate_coo and compare only).  Vectors are float for F32 / F16 matrices and double for F64 (the convention of bmsp_spmv's u and of
+ * bmsp_matrix_row_absmax), indexed by MATRIX row / column whatever the tile layout.  No pass sorts, scans, reads back or uses an atomic.
+ *   bmsp_matrix_diagonal: d_diag receives min(num_rows, num_cols) entries; entry i is the stored value at (i, i) widened exactly (F32 /
+ *       F64 as raw bits: -0, NaN payloads and subnormals survive; F16 widened to float), +0 where (i, i) is not stored -- the call writes
+ *       every entry itself, the buffer needs no clearing.  Either tile layout.  A is not modified (its block-row pointer is built if
+ *       missing).  Asynchronous on `stream`.
+ *   bmsp_matrix_from_diagonal: a fresh pool-owned num_rows x num_cols matrix with d_diag[i] stored at every (i, i), i < min(num_rows,
+ *       num_cols), zeros included (the library keeps what it is given; bmsp_matrix_prune is the call that drops).  Its four arrays and
+ *       block-row pointer equal, bit for bit, what bmsp_matrix_from_coo makes from the triples (i, i, d_diag[i]) in layout `transposed`:
+ *       tile t has key (t << 32) | t, the positions 0, 9, .., 63 (cut to the count of the last tile) and offset 8t.  F16 values are rounded
+ *       from the float input by the builder's round-to-nearest-even conversion.  min(num_rows, num_cols) == 0 gives a valid matrix of 0
+ *       tiles with offsets = [0] (d_diag may then be NULL).  Asynchronous on `stream`.
+ *   bmsp_matrix_scale: out = diag(l) * A * diag(r), l = d_left (num_rows entries), r = d_right (num_cols entries).  Either pointer may be
+ *       NULL: that side is skipped, not multiplied by 1; with both NULL the call is bmsp_matrix_convert_layout, bit for bit.  `out` is a
+ *       fresh pool-owned handle of A's shape and dtype with tiles in layout out_transposed (A may have either); its keys, bitmaps,
+ *       offsets and block-row pointer equal bmsp_matrix_convert_layout(A, out_transposed)'s: every coordinate is kept, results that are
+ *       0, Inf or NaN included.  Values: the left factor first, then the right, each operation rounded on its own.  F32:
+ *       c = fl32(fl32(l o a) o r), each o an IEEE multiply, or an IEEE divide x / d under BMSP_SCALE_DIV_LEFT / _RIGHT for that side
+ *       (the full division sequence, never a reciprocal).  F64 the same in double.  F16: a is widened exactly, the F32 formula is
+ *       evaluated in fp32 and the result rounded once to fp16, round-to-nearest-even (it may overflow to +-Inf).  Subnormal inputs and
+ *       results are kept; x / 0, 0 / 0, 0 * Inf give what IEEE gives.  A and its caches are not modified.  The output remembers A as a
+ *       layout conversion does, so bmsp_matrix_scale_values and bmsp_matrix_copy_values accept it.  Asynchronous on `stream`: unlike its
+ *       siblings the call does NOT synchronise (nothing is read back, no temporary is allocated); synchronise the stream before reading
+ *       the arrays from another stream or the host.
+ *   bmsp_matrix_scale_values: the same value pass into an existing matrix.  out == A scales A in place.  Otherwise `out` must have been
+ *       made from A by bmsp_matrix_scale or bmsp_matrix_convert_layout while A's STRUCTURE has not changed since (its uid, renewed by
+ *       bmsp_matrix_invalidate(A, 1)); anything else -- an unrelated handle, a bmsp_matrix_transpose output -- is BMSP_ERR_INVALID.
+ *       Drops out's value-derived caches as bmsp_matrix_copy_values does (dense tiles, lane tiles, CSR copy, finite flags), an in-place
+ *       A's included; its SpMV plan and position cache stay.  Asynchronous on `stream` unless out holds such caches (dropping them
+ *       synchronises the device).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalar arguments before handles: flags with unknown bits;
+ *   out_transposed / transposed not 0 / 1; a dtype that is none of the three; negative num_rows / num_cols; a DIV flag whose vector is
+ *   NULL; null A, out, d_diag (bmsp_matrix_from_diagonal: only while min(num_rows, num_cols) > 0); row-panel views. */
+int bmsp_matrix_diagonal(bmsp_matrix_t A, void *d_diag, void *stream);
+int bmsp_matrix_from_diagonal(int num_rows, int num_cols, const void *d_diag, bmsp_dtype dtype, int transposed, void *stream,
+                              bmsp_matrix_t *out);
+#define BMSP_SCALE_DIV_LEFT  1   /* divide by d_left[row] instead of multiplying  */
+#define BMSP_SCALE_DIV_RIGHT 2   /* divide by d_right[col] instead of multiplying */
+int bmsp_matrix_scale(bmsp_matrix_t A, const void *d_left, const void *d_right, int flags, int out_transposed, void *stream,
+                      bmsp_matrix_t *out);
+int bmsp_matrix_scale_values(bmsp_matrix_t A, const void *d_left, const void *d_right, int flags, bmsp_matrix_t out,
+                             void *stream);
 /* dense block-row pointer (num_block_rows+1 uint32 entries) the operators use; built once and cached
  * (the reference rebuilds a compressed one on every call, src/bmSparse_SPMV.cu:199-206). */
 int bmsp_matrix_block_row_ptr(bmsp_matrix_t m, const uint32_t **d_rowptr, int64_t *num_block_rows);
