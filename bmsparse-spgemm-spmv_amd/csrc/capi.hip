@@ -723,6 +723,14 @@ int bmsp_spmm(bmsp_matrix_t A, const void *d_X, int64_t ldx, void *d_Y, int64_t 
     BMSP_API_END
 }
 
+int bmsp_spmm_launch_info(bmsp_matrix_t A, int k, int64_t ldx, int64_t ldy, char *kernel_name, size_t kernel_name_cap)
+{
+    BMSP_API_BEGIN
+    need(A, "A");
+    spmm_launch_info(A, k, ldx, ldy, nullptr, kernel_name, kernel_name_cap);
+    BMSP_API_END
+}
+
 int bmsp_spgemm(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t *C, int mode, int tc_version, int verbose, void *stream,
                 bmsp_spgemm_stats *stats)
 {

@@ -16,6 +16,7 @@
 // write-through store + agent-scope counter hand-off as the SpMV, so the result does not depend on arrival order).
 #include "spmv_plan.h"
 #include <cstdlib>
+#include <cstdio>
 #include "prims.hip.h"
 
 namespace bmsp {
@@ -436,43 +437,89 @@ void launch_kk(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ld
     if (A->spmv_plan_long) BMSP_HIP(hipStreamSynchronize(st));  // the carry slots go back to the pool on return
 }
 
-template <typename T>
-void launch(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st)
+// ---- which kernel runs: decided in ONE place, for the launcher and for bmsp_spmm_launch_info ---------------------------------------
+enum class SpmmPath { kNone, kSpmv, kVstream4, kVstream8, kSlot4, kSlot16, kSlot64, kWide };
+
+const char *path_name(SpmmPath p)
 {
+    switch (p) {
+    case SpmmPath::kNone: return "none (empty matrix)";
+    case SpmmPath::kSpmv: return "spmv";  // spmm_launch_info appends the SpMV's own kernel name
+    case SpmmPath::kVstream4: return "spmm_vstream_kernel<4>";
+    case SpmmPath::kVstream8: return "spmm_vstream_kernel<8>";
+    case SpmmPath::kSlot4: return "spmm_kernel<4>";
+    case SpmmPath::kSlot16: return "spmm_kernel<16>";
+    case SpmmPath::kSlot64: return "spmm_kernel<64>";
+    case SpmmPath::kWide: return "spmm_wide_kernel";
+    }
+    return "";
+}
+
+void check_args(const bmsp_matrix_s *A, int64_t ldx, int64_t ldy, int k)
+{
+    if (A->transposed) fail(BMSP_ERR_INVALID, "SpMM needs a matrix built with transposed=0");
+    if (k < 1) fail(BMSP_ERR_INVALID, "k must be >= 1");
+    if (ldx < k || ldy < k) fail(BMSP_ERR_INVALID, "leading dimensions must be >= k");
+}
+
+// the path bmsp_spmm takes for (A, k, ldx, ldy); builds what that path reads (block-row pointer, plan, position cache)
+SpmmPath choose_path(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStream_t st)
+{
+    if (A->num_rows == 0) return SpmmPath::kNone;
+    if (k == 1 && ldx == 1 && ldy == 1) return SpmmPath::kSpmv;  // one contiguous vector: the SpMV itself
+    ensure_rowptr(A, st);
+    build_plan(A, st);
+    prepare_spmv(A, st);  // + the position cache, for matrices the value-stream kernels take
     // measured on the webbase-1M-like case: the time is set by tiles x vector chunks (each wave walks its tiles
     // serially), so the widest lane group that k fills wins
     // k <= 8 on a matrix that carries the SpMV position cache (sparse tiles): the value-stream walk
-    if (A->spmv_pos && k <= 8 && !getenv("BMSP_SPMM_NO_VSTREAM")) {
-        if (k <= 4) launch_vstream<T, 4>(A, X, ldx, Y, ldy, k, st);
-        else launch_vstream<T, 8>(A, X, ldx, Y, ldy, k, st);
-        return;
+    if (A->spmv_pos && k <= 8 && !getenv("BMSP_SPMM_NO_VSTREAM")) return k <= 4 ? SpmmPath::kVstream4 : SpmmPath::kVstream8;
+    if (k <= 4) return SpmmPath::kSlot4;
+    if (k <= 16) return SpmmPath::kSlot16;
+    if ((uint64_t)A->values_extent() < (1ull << 32)) return SpmmPath::kWide;  // 32-bit value indices in the stream
+    return SpmmPath::kSlot64;
+}
+
+template <typename T>
+void launch(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st)
+{
+    switch (choose_path(A, k, ldx, ldy, st)) {
+    case SpmmPath::kNone: break;
+    case SpmmPath::kSpmv: spmv(A, X, Y, BMSP_SPMV_DEFAULT, st); break;
+    case SpmmPath::kVstream4: launch_vstream<T, 4>(A, X, ldx, Y, ldy, k, st); break;
+    case SpmmPath::kVstream8: launch_vstream<T, 8>(A, X, ldx, Y, ldy, k, st); break;
+    case SpmmPath::kSlot4: launch_kk<T, 4>(A, X, ldx, Y, ldy, k, st); break;
+    case SpmmPath::kSlot16: launch_kk<T, 16>(A, X, ldx, Y, ldy, k, st); break;
+    case SpmmPath::kSlot64: launch_kk<T, 64>(A, X, ldx, Y, ldy, k, st); break;
+    case SpmmPath::kWide: launch_wide<T>(A, X, ldx, Y, ldy, k, st); break;
     }
-    if (k <= 4) launch_kk<T, 4>(A, X, ldx, Y, ldy, k, st);
-    else if (k <= 16) launch_kk<T, 16>(A, X, ldx, Y, ldy, k, st);
-    else if ((uint64_t)A->values_extent() < (1ull << 32)) launch_wide<T>(A, X, ldx, Y, ldy, k, st);  // 32-bit value indices in the stream
-    else launch_kk<T, 64>(A, X, ldx, Y, ldy, k, st);
 }
 
 }  // namespace
 
 void spmm(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st)
 {
-    if (A->transposed) fail(BMSP_ERR_INVALID, "SpMM needs a matrix built with transposed=0");
-    if (k < 1) fail(BMSP_ERR_INVALID, "k must be >= 1");
-    if (ldx < k || ldy < k) fail(BMSP_ERR_INVALID, "leading dimensions must be >= k");
-    if (A->num_rows == 0) return;
-    if (k == 1 && ldx == 1 && ldy == 1) {  // one contiguous vector: the SpMV itself
-        spmv(A, X, Y, BMSP_SPMV_DEFAULT, st);
-        return;
-    }
-    ensure_rowptr(A, st);
-    build_plan(A, st);
-    prepare_spmv(A, st);  // + the position cache, for matrices the value-stream kernels take
+    check_args(A, ldx, ldy, k);
     switch (A->dtype) {
     case BMSP_F32: launch<float>(A, X, ldx, Y, ldy, k, st); break;
     case BMSP_F16: launch<_Float16>(A, X, ldx, Y, ldy, k, st); break;
     case BMSP_F64: launch<double>(A, X, ldx, Y, ldy, k, st); break;
     default: fail(BMSP_ERR_INVALID, "unknown dtype");
+    }
+}
+
+// the name of the kernel spmm() launches for these arguments: choose_path() is the launcher's own decision
+void spmm_launch_info(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStream_t st, char *kernel, size_t kernel_cap)
+{
+    check_args(A, ldx, ldy, k);
+    const SpmmPath p = choose_path(A, k, ldx, ldy, st);
+    if (!kernel || !kernel_cap) return;
+    if (p == SpmmPath::kSpmv) {
+        char sub[96];
+        spmv_launch_info(A, BMSP_SPMV_DEFAULT, st, sub, sizeof sub, nullptr, nullptr);
+        snprintf(kernel, kernel_cap, "spmv: %s", sub);
+    } else {
+        snprintf(kernel, kernel_cap, "%s", path_name(p));
     }
 }
 

@@ -284,8 +284,18 @@ int bmsp_spmv_launch_info(bmsp_matrix_t A, int variant, char *kernel_name, size_
 
 /* SURVEY 8(f)3 -- Y = A * X for k vectors at once (what the reference's unfinished `batched` path points at,
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
- * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k. */
+ * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
+ * Every Y[i][j], i < num_rows, j < k, is written (0 for a row without stored values); the padding columns j >= k of a strided Y
+ * and of X are neither written nor read into the result.  On a row-panel view (bmsp_matrix_row_panel) the view keeps the parent's
+ * num_rows, so the rows outside the panel are rows without stored values: they are written as exact 0, not left untouched. */
 int bmsp_spmm(bmsp_matrix_t A, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, int k, void *stream);
+
+/* The kernel bmsp_spmm(A, X, ldx, Y, ldy, k) launches, by name: "spmm_vstream_kernel<4>" / "<8>", "spmm_kernel<4>" / "<16>" / "<64>",
+ * "spmm_wide_kernel", "spmv: <bmsp_spmv_launch_info's name>" when the call is handed to the SpMV (k = 1, unit strides), or
+ * "none (empty matrix)" for a matrix of zero rows (a matrix with rows but no stored value launches a kernel: it writes the zeros).
+ * Same argument checks and the same preparation as bmsp_spmm (block-row pointer, plan, position cache); the choice is made by the
+ * function the launcher itself calls.  Reporting only (tests pin kernels with it). */
+int bmsp_spmm_launch_info(bmsp_matrix_t A, int k, int64_t ldx, int64_t ldy, char *kernel_name, size_t kernel_name_cap);
 
 /* per-stage figures of one product: the lines the reference prints when VERBOSE
  * (src/bmSparse_SPGEMM.cu:849-1220) plus what the roofline needs. */
