@@ -246,15 +246,35 @@ void read_matrix_market(const std::string &path_in, HostCoo &out)
 // ------------------------------------------------------------------------------------------------
 namespace {
 
+// What the kernels of one build tell the host about malformed input: a pinned host word the host clears before the first launch and a
+// kernel sets (a plain store, taken on a bad entry only).  The host looks at it once the stream has been synchronised behind every
+// kernel that can set it; with nnz > 0 that is the builder's one read-back, so the check costs the valid path no launch and no
+// synchronisation of its own.
+struct BadInput {
+    HostScalar<uint32_t> slot;
+    BadInput() { *(volatile uint32_t *)slot.p = 0u; }
+    uint32_t *dev() const { return slot.dev(); }
+    // a plain load: the caller has synchronised the stream the kernels ran on (which also lets the slot go back to its pool)
+    bool raised_after_sync() const
+    {
+        slot.done = true;
+        return *(volatile uint32_t *)slot.p != 0u;
+    }
+};
+
 struct MakeSortKey {
     const int *rows, *cols;
     uint64_t *keys;
     uint32_t *perm;
     int cbits;
     int transposed;
+    uint32_t num_rows, num_cols;
+    uint32_t *bad;
     __device__ void operator()(uint64_t i) const
     {
         uint32_t r = (uint32_t)rows[i], c = (uint32_t)cols[i];
+        // an index outside the shape (negative ones compare as large) would set key bits the sort does not look at
+        if (r >= num_rows || c >= num_cols) *bad = 1u;
         // intra-tile position: coord_to_bmp (src/bmSpMatrix.cu:85-98)
         uint32_t pos = transposed ? ((c & 7u) << 3) | (r & 7u) : ((r & 7u) << 3) | (c & 7u);
         keys[i] = ((uint64_t)(r >> 3) << (cbits + 6)) | ((uint64_t)(c >> 3) << 6) | pos;
@@ -706,11 +726,11 @@ void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st)
     if (m->dtype != BMSP_F64) ensure_finite_flag(m, st);
 }
 
-bmsp_matrix_s *build_from_device_coo(int num_rows, int num_cols, int64_t nnz, const int *d_rows, const int *d_cols,
-                                     const double *d_vals, int transposed, bmsp_dtype dtype, hipStream_t st)
+namespace {
+// `bad` may already have been handed to a kernel launched on `st` (the CSR entry point's row search); `launched` says so
+bmsp_matrix_s *build_checked(int num_rows, int num_cols, int64_t nnz, const int *d_rows, const int *d_cols, const double *d_vals,
+                             int transposed, bmsp_dtype dtype, hipStream_t st, const BadInput &bad, bool launched)
 {
-    if (num_rows < 0 || num_cols < 0 || nnz < 0) fail(BMSP_ERR_INVALID, "negative dimension");
-    if (nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "nnz %lld exceeds the 32-bit element range", (long long)nnz);
     auto m = make_matrix();
     m->num_rows = num_rows; m->num_cols = num_cols; m->dtype = dtype; m->transposed = transposed ? 1 : 0;
     uint64_t n = (uint64_t)nnz;
@@ -719,14 +739,21 @@ bmsp_matrix_s *build_from_device_coo(int num_rows, int num_cols, int64_t nnz, co
 
     DevBuf<uint64_t> k0(n), k1(n);
     DevBuf<uint32_t> p0(n), p1(n);
-    device_for_each(MakeSortKey{d_rows, d_cols, k0.p, p0.p, cbits, m->transposed}, n, st);
+    device_for_each(MakeSortKey{d_rows, d_cols, k0.p, p0.p, cbits, m->transposed, (uint32_t)num_rows, (uint32_t)num_cols, bad.dev()}, n, st);
     PingPong<uint64_t> kk{k0.p, k1.p};
     PingPong<uint32_t> pp{p0.p, p1.p};
     device_radix_sort_pairs<uint32_t>(kk, pp, n, 0, rbits + cbits + 6, st);
 
     DevBuf<uint64_t> totals(1);
     device_exclusive_scan<uint64_t>(HeadFlags{kk.cur, n}, CountOut{n, totals.p}, n + 1, st);
-    uint64_t packed = n ? read_back(totals.p, st) : 0;
+    // the synchronise BadInput needs: the read-back's own, or (no entries, so no read-back; only the CSR entry point has launched
+    // anything, its check of the offsets) an explicit one.  Nothing is allocated for the matrix yet.
+    uint64_t packed = 0;
+    if (n) packed = read_back(totals.p, st);
+    else if (launched) BMSP_HIP(hipStreamSynchronize(st));
+    if (bad.raised_after_sync())
+        fail(BMSP_ERR_INVALID, "malformed input: an index outside %dx%d%s", num_rows, num_cols,
+             launched ? ", or row offsets that do not run from 0 to nnz without decreasing" : "");
     m->block_num = (int64_t)(packed >> 32);
     m->nnz = (int64_t)(packed & 0xffffffffull);
     alloc_tile_arrays(m.get(), (uint64_t)m->block_num);
@@ -739,6 +766,22 @@ bmsp_matrix_s *build_from_device_coo(int num_rows, int num_cols, int64_t nnz, co
     ensure_rowptr(m.get(), st);
     BMSP_HIP(hipStreamSynchronize(st));  // temporaries go back to the pool below
     return m.release();
+}
+
+void check_build_args(int num_rows, int num_cols, int64_t nnz, bmsp_dtype dtype)
+{
+    if (num_rows < 0 || num_cols < 0 || nnz < 0) fail(BMSP_ERR_INVALID, "negative dimension");
+    if (nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "nnz %lld exceeds the 32-bit element range", (long long)nnz);
+    if (dtype != BMSP_F32 && dtype != BMSP_F16 && dtype != BMSP_F64) fail(BMSP_ERR_INVALID, "unknown dtype %d", (int)dtype);
+}
+}  // namespace
+
+bmsp_matrix_s *build_from_device_coo(int num_rows, int num_cols, int64_t nnz, const int *d_rows, const int *d_cols,
+                                     const double *d_vals, int transposed, bmsp_dtype dtype, hipStream_t st)
+{
+    check_build_args(num_rows, num_cols, nnz, dtype);
+    BadInput bad;
+    return build_checked(num_rows, num_cols, nnz, d_rows, d_cols, d_vals, transposed, dtype, st, bad, false);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -850,12 +893,24 @@ struct RowOffsetsFromSorted {
         for (uint32_t r = lo; r <= hi; r++) row_offsets[r] = (int)i;
     }
 };
+// The row of every entry, and the contract of the offsets on the way: thread i looks at the pair (i, i + 1) -- offsets start at 0, end
+// at nnz and never decrease -- so the launch covers max(nnz, num_rows + 1) threads, and an empty matrix, which had no launch at all,
+// now has this one and a synchronise to read its verdict.  The search itself only ever reads
+// row_offsets[1 .. num_rows - 1] and writes rows[i], whatever the offsets hold.
 struct RowOfEntry {
     const int *row_offsets;
     uint32_t num_rows;
+    uint64_t nnz;
     int *rows;
+    uint32_t *bad;
     __device__ void operator()(uint64_t i) const
     {
+        if (i <= num_rows) {
+            const int64_t a = row_offsets[i];
+            const bool ok = (i != 0 || a == 0) && (i == num_rows ? a == (int64_t)nnz : a <= (int64_t)row_offsets[i + 1]);
+            if (!ok) *bad = 1u;
+        }
+        if (i >= nnz) return;
         uint32_t lo = 0, hi = num_rows;  // last r with row_offsets[r] <= i
         while (hi - lo > 1) {
             const uint32_t mid = (lo + hi) >> 1;
@@ -972,9 +1027,11 @@ void matrix_to_csr_device(bmsp_matrix_s *m, int *d_row_offsets, int *d_cols, dou
 bmsp_matrix_s *build_from_device_csr(int num_rows, int num_cols, int64_t nnz, const int *d_row_offsets, const int *d_cols, const double *d_vals,
                                      int transposed, bmsp_dtype dtype, hipStream_t st)
 {
+    check_build_args(num_rows, num_cols, nnz, dtype);
+    BadInput bad;
     DevBuf<int> rows((size_t)nnz);
-    if (nnz) device_for_each(RowOfEntry{d_row_offsets, (uint32_t)num_rows, rows.p}, (uint64_t)nnz, st);
-    return build_from_device_coo(num_rows, num_cols, nnz, rows.p, d_cols, d_vals, transposed, dtype, st);
+    device_for_each(RowOfEntry{d_row_offsets, (uint32_t)num_rows, (uint64_t)nnz, rows.p, bad.dev()}, std::max<uint64_t>((uint64_t)nnz, (uint64_t)num_rows + 1), st);
+    return build_checked(num_rows, num_cols, nnz, rows.p, d_cols, d_vals, transposed, dtype, st, bad, true);
 }
 
 }  // namespace bmsp

@@ -287,6 +287,15 @@ class BmSpMatrix:
                                          vals.ctypes.data, int(bool(transposed)), dtype, C.byref(h)))
         return BmSpMatrix(h.value)
 
+    @staticmethod
+    def from_coo_device(num_rows, num_cols, rows, cols, vals, transposed=False, dtype=F32, stream=None):
+        """rows / cols int32, vals float64 DeviceArrays of equal length (bmsp_matrix_from_coo_device)."""
+        assert rows.n == cols.n == vals.n
+        h = C.c_void_p()
+        check(lib().bmsp_matrix_from_coo_device(int(num_rows), int(num_cols), rows.n, rows.ptr, cols.ptr, vals.ptr,
+                                                int(bool(transposed)), dtype, stream, C.byref(h)))
+        return BmSpMatrix(h.value)
+
     # bmSpMatrix(int num_rows, int num_cols, int block_num, keys&, bmps&, offsets&, values&)
     @staticmethod
     def from_arrays(num_rows, num_cols, keys, bmps, offsets, values, dtype=F32, transposed=False):

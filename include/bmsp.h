@@ -82,7 +82,10 @@ int bmsp_matrix_from_mtx(const char *path, int transposed, bmsp_dtype dtype, bms
 int bmsp_matrix_from_coo(int num_rows, int num_cols, int64_t nnz, const int *rows, const int *cols,
                          const double *vals, int transposed, bmsp_dtype dtype, bmsp_matrix_t *out);
 
-/* Same builder from COO triples already resident on the device (rows/cols int32, vals float64). */
+/* Same builder from COO triples already resident on the device (rows/cols int32, vals float64).  The contract is that of
+ * bmsp_matrix_from_coo: every index lies in [0, num_rows) x [0, num_cols) and dtype is one of the three bmsp_dtype values.
+ * The builder's own kernels check it on the device (no extra launch or synchronisation); a violation returns
+ * BMSP_ERR_INVALID, leaves *out untouched and nothing allocated. */
 int bmsp_matrix_from_coo_device(int num_rows, int num_cols, int64_t nnz, const int *d_rows, const int *d_cols,
                                 const double *d_vals, int transposed, bmsp_dtype dtype, void *stream,
                                 bmsp_matrix_t *out);
@@ -247,7 +250,10 @@ int bmsp_matrix_to_coo_host(bmsp_matrix_t m, int *rows, int *cols, double *vals)
  * feed CSR consumers without a host round trip.  d_rows/d_cols/d_vals hold nnz entries, d_row_offsets num_rows+1. */
 int bmsp_matrix_to_coo_device(bmsp_matrix_t m, int *d_rows, int *d_cols, double *d_vals, void *stream);
 int bmsp_matrix_to_csr_device(bmsp_matrix_t m, int *d_row_offsets, int *d_cols, double *d_vals, void *stream);
-/* ... and the builder from a device-resident CSR (int32 offsets/columns, float64 values; duplicates summed as in from_coo). */
+/* ... and the builder from a device-resident CSR (int32 offsets/columns, float64 values; duplicates summed as in from_coo).
+ * Contract, checked on the device like bmsp_matrix_from_coo_device's (for nnz == 0 at the price of one small launch and a
+ * synchronise, which an empty matrix did not have): d_row_offsets[0] == 0, d_row_offsets[num_rows] == nnz, no
+ * offset larger than the next, every column in [0, num_cols), a known dtype; otherwise BMSP_ERR_INVALID and no matrix. */
 int bmsp_matrix_from_csr_device(int num_rows, int num_cols, int64_t nnz, const int *d_row_offsets, const int *d_cols,
                                 const double *d_vals, int transposed, bmsp_dtype dtype, void *stream, bmsp_matrix_t *out);
 

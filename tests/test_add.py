@@ -325,10 +325,7 @@ def coo_route(bmsp, A, B, lay):
     rb, cb, vb = B.to_coo_device()
     r, c, v = (_device_concat(bmsp, [x, y], t) for x, y, t in ((ra, rb, np.int32), (ca, cb, np.int32), (va, vb, np.float64)))
     i = A.info()
-    h = C.c_void_p()
-    bmsp.check(bmsp.lib().bmsp_matrix_from_coo_device(i["num_rows"], i["num_cols"], r.n, r.ptr, c.ptr, v.ptr, int(lay), i["dtype"], None,
-                                                      C.byref(h)))
-    return bmsp.BmSpMatrix(h.value)
+    return bmsp.BmSpMatrix.from_coo_device(i["num_rows"], i["num_cols"], r, c, v, transposed=lay, dtype=i["dtype"])
 
 
 def test_headline_rmat20_a_plus_at_matches_coo_route(bmsp):

@@ -619,9 +619,7 @@ def test_headline_rmat20_matches_the_builder_of_the_scaled_coo(bmsp):
         sv = ((cv.astype(np.float32) * l[cr]) / rt[cc]).astype(np.float64)
     ddr, ddc, ddv = (bmsp.DeviceArray.from_host(x) for x in (cr, cc, sv))
     for lout in (0, 1):
-        h = C.c_void_p()
-        bmsp.check(bmsp.lib().bmsp_matrix_from_coo_device(n, n, ddr.n, ddr.ptr, ddc.ptr, ddv.ptr, lout, 0, None, C.byref(h)))
-        ref = bmsp.BmSpMatrix(h.value)
+        ref = bmsp.BmSpMatrix.from_coo_device(n, n, ddr, ddc, ddv, transposed=lout)
         S = bmsp.scale(A, dl, dr, div_right=True, transposed=lout)
         assert_same_arrays(S, ref)
         np.testing.assert_array_equal(S.block_row_ptr(), ref.block_row_ptr())

@@ -524,9 +524,7 @@ def test_headline_rmat20_matches_the_builder_of_the_filtered_coo(bmsp):
     assert abs(keep.mean() - 2 / 3) < 0.01
     dr, dc, dv = (bmsp.DeviceArray.from_host(x[keep]) for x in (cr, cc, cv))
     for lout in (0, 1):
-        h = C.c_void_p()
-        bmsp.check(bmsp.lib().bmsp_matrix_from_coo_device(n, n, dr.n, dr.ptr, dc.ptr, dv.ptr, lout, 0, None, C.byref(h)))
-        ref = bmsp.BmSpMatrix(h.value)
+        ref = bmsp.BmSpMatrix.from_coo_device(n, n, dr, dc, dv, transposed=lout)
         P, st = bmsp.prune(A, 0.0, transposed=lout)
         assert st["nnz_out"] == int(keep.sum()) and st["blocks_out"] == ref.block_num < A.block_num
         assert_same_arrays(P, ref)
