@@ -449,7 +449,7 @@ void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)
     m->sp_tasks = nullptr; m->sp_task_begin = nullptr; m->sp_c_of_wave = nullptr; m->sp_n_tasks = 0;
     pool_free(m->spmv_chunks); m->spmv_chunks = nullptr; m->spmv_num_chunks = 0; m->spmv_plan_long = 0; m->spmv_full_tiles = 0;
     pool_free(m->spmv_pos); m->spmv_pos = nullptr; m->spmv_tinfo = nullptr; m->spmv_eoff = nullptr; m->spmv_pos_base = 0; m->spmv_pos_count = 0; m->spmv_pos_tried = 0;
-    pool_free(m->spmv_cw); m->spmv_cw = nullptr; m->spmv_cw_chunks = 0; m->spmv_cw_split = 0; m->spmv_cw_tried = 0;
+    pool_free(m->spmv_cw); m->spmv_cw = nullptr; m->spmv_cw_chunks = 0; m->spmv_cw_split = 0; m->spmv_cw_tried = 0; m->spmv_cw_layout = 0;
     pool_free(m->block_meta); m->block_meta = nullptr;
     pool_free(m->sym_recs); m->sym_recs = nullptr;
     pool_free(m->col_index); pool_free(m->col_index_row); m->col_index = nullptr; m->col_index_row = nullptr; m->col_index_tried = 0;

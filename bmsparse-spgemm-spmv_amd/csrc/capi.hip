@@ -590,6 +590,14 @@ int bmsp_spmv_launch_info(bmsp_matrix_t A, int variant, char *kernel_name, size_
     BMSP_API_END
 }
 
+int bmsp_spmv_chunk_layout(bmsp_matrix_t A, int *layout)
+{
+    BMSP_API_BEGIN
+    need(A, "A"); need(layout, "layout");
+    *layout = spmv_chunk_layout(A, nullptr);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

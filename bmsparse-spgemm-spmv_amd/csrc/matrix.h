@@ -40,11 +40,12 @@ struct bmsp_matrix_s {
     int64_t spmv_pos_base = 0, spmv_pos_count = 0;
     int spmv_pos_tried = 0;
     // chunked sweep (spmv_chunk_kernel): one 32-bit word {row relative to the chunk's first block-row, column} per stored value, padded to
-    // whole chunks | chunk records | arrival counters | carry slots -- one allocation, structure only (kept across value-only invalidation)
+    // whole chunks | chunk records | arrival counters | carry slots -- one allocation, structure only (kept across value-only invalidation).
+    // spmv_cw_layout: 1 = the words in storage order (round 7), 2 = row-sorted words {column, storage index, run start, window bitmap bits}
     uint32_t *spmv_cw = nullptr;
     int64_t spmv_cw_chunks = 0, spmv_cw_split = 0;  // chunks; block-rows folded across chunks
     size_t spmv_cw_off_rec = 0, spmv_cw_off_cnt = 0, spmv_cw_off_carry = 0;
-    int spmv_cw_colbits = 0, spmv_cw_tried = 0;
+    int spmv_cw_colbits = 0, spmv_cw_tried = 0, spmv_cw_layout = 0;
     // (bitmap, value offset) of every block as one 16-byte record, for kernels that gather both (block-MAC): built lazily
     uint32_t *block_meta = nullptr;  // block_num x {bmp lo, bmp hi, offset in elements, 0}
     uint32_t *sym_recs = nullptr;    // right operands: block_num x {bitmap ROW-major (lo, hi), block column, rows the tile uses}: all the column-window passes (rowwindow.hip) read per candidate pair
@@ -227,6 +228,7 @@ void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);
 
 void spmv(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t st, int64_t row_lo = 0, int64_t row_hi = -1);
 void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kernel, size_t kernel_cap, int64_t *compulsory, int64_t *format_bytes);
+int spmv_chunk_layout(bmsp_matrix_s *A, hipStream_t st);
 void spmm(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st);
 void spmm_launch_info(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStream_t st, char *kernel, size_t kernel_cap);
 void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **C, int mode, int tc_version, int verbose, hipStream_t st,

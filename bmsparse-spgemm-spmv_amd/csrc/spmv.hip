@@ -38,6 +38,7 @@
 #include "spmv_plan.h"
 #include "prims.hip.h"
 #include <cstdlib>
+#include <cstring>
 #include <cstdio>
 #include <algorithm>
 #include <vector>
@@ -1241,6 +1242,113 @@ __device__ __forceinline__ void chunk_fold(const float *__restrict__ carry, floa
     if (lane == 0) __hip_atomic_store(&counters[ca], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the row-sorted form (round 9, layout 2; colbits <= kChSortedColbits) ----
+// Which values of a chunk share a row is fixed per matrix, so the cache build (chunk_sort_kernel) groups them once: the chunk's 512 words
+// are stored in ROW order (positions sorted by row, ties in storage order), and word p holds
+//   bits 0 .. colbits-1  the column of the value at position p
+//   next 9               its storage index inside the chunk (values[512 c + idx])
+//   next 1               start: position p begins a new row (p = 0: always)
+//   next 2               bits 2p and 2p+1 of the chunk's window bitmap (bit e: row 8 fb + e has a value in this chunk; 1024 bits)
+// -- the same 4 bytes per stored value.  Positions past nnz (last chunk) are 0 apart from their bitmap bits: they continue the last run and
+// add an exact +0 (no x read).  The sweep is left with ONE sum per lane: products in row order, a sequential segmented sum in the lane, the
+// wave_run_sum steps on one float across lanes, and every run's last position stores the run total to T[run rank].  Row e of the window is
+// T[number of bitmap bits below e] when bit e is set, else 0: no zero-filled window, no per-block-row sums.
+constexpr int kChSortedColbits = 20;           // 20 + 9 + 1 + 2 = 32 bits
+constexpr uint32_t kChT = kChV + 64;           // run totals, then one dump slot per lane (positions that end no run store there)
+constexpr uint32_t kChSortedLds = kChT + 64;   // ... | 32 bitmap words | 32 counts of bits below each word
+static_assert(kChSortedLds * 4 <= 6144, "the row-sorted form keeps to 6 KB of LDS per wave");
+
+__device__ __forceinline__ float chunk_row_value(const float *T, const uint32_t *bmw, const uint32_t *pre, uint32_t e)
+{
+    const uint32_t wd = bmw[e >> 5], sh = e & 31u;
+    const float v = T[pre[e >> 5] + (uint32_t)__popc(wd & ((1u << sh) - 1u))];  // <= kChV (the first dump slot) when bit e is clear
+    return (wd >> sh) & 1u ? v : 0.f;
+}
+
+// one chunk of the row-sorted form, up to the row sums: on return T, the bitmap words and their prefix counts are in lds.  WHOLE: the chunk
+// holds kChV values (every chunk but the last) -- 16-byte value loads and no bound on the positions; the two cases are separate code so
+// that the gathers of the common one wait for the words alone.  lds: first the values in storage order, then (the same floats) T.
+template <bool WHOLE>
+__device__ __forceinline__ void chunk_sorted_reduce(float *lds, const uint32_t *__restrict__ words, const float *__restrict__ values,
+                                                    const float *__restrict__ x, uint32_t c, uint32_t nnz, uint32_t num_cols, uint32_t colbits, int lane)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const uint32_t first = c * kChV + (uint32_t)(kChPer * lane), nval = WHOLE ? kChV : nnz - c * kChV;
+    // the words are padded to whole chunks (the padding carries bitmap bits): always 16-byte loads, both requested before the values
+    const rsrc_t rw = make_rsrc(words, (uint32_t)min((uint64_t)gridDim.x * kChV * 4u, (uint64_t)0xfffffffcu));
+    const rsrc_t rv = make_rsrc(values, nnz * 4u), rx = make_rsrc(x, num_cols * 4u);
+    uint32_t w[kChPer];
+    float a[kChPer], xv[kChPer];
+#pragma unroll
+    for (int q = 0; q < kChPer; q += 4) {
+        const u4 wq = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rw, (first + q) * 4u, 0, 0));
+#pragma unroll
+        for (int i = 0; i < 4; i++) w[q + i] = wq[i];
+    }
+    if constexpr (WHOLE) {
+#pragma unroll
+        for (int q = 0; q < kChPer; q += 4) {
+            const f4 aq = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (first + q) * 4u, 0, 0));
+#pragma unroll
+            for (int i = 0; i < 4; i++) a[q + i] = aq[i];
+        }
+    } else {  // element loads, values past nnz read 0
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) a[j] = Buf<float>::ld(rv, first + j < nnz ? (first + j) * 4u : kOob);
+    }
+    const uint32_t cmask = (1u << colbits) - 1u;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) xv[j] = Buf<float>::ld(rx, WHOLE || (uint32_t)(kChPer * lane + j) < nval ? (w[j] & cmask) * 4u : kOob);
+    float *T = lds;
+    uint32_t *bmw = (uint32_t *)(lds + kChT), *pre = bmw + 32;
+    chunk_put8(T + kChPer * lane, a);
+    uint32_t bits = 0;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) bits |= (w[j] >> (colbits + 10u)) << (2 * j);
+    ((uint16_t *)bmw)[lane] = (uint16_t)bits;
+    __builtin_amdgcn_wave_barrier();
+    float pr[kChPer];
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) pr[j] = T[(w[j] >> colbits) & (kChV - 1u)];
+    {
+        const uint32_t wd = lane < 32 ? bmw[lane] : 0u, pc = (uint32_t)__popc(wd);
+        const uint32_t below = wave_inclusive_sum_dpp(pc) - pc;
+        if (lane < 32) pre[lane] = below;
+    }
+    // run rank of every position: starts up to and including it, minus one
+    uint32_t st[kChPer], k[kChPer], tot = 0;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) {
+        st[j] = (w[j] >> (colbits + 9u)) & 1u;
+        tot += st[j];
+        k[j] = tot;
+    }
+    const uint32_t base = wave_inclusive_sum_dpp(tot) - tot - 1u;
+#pragma unroll
+    for (int j = 0; j < kChPer; j++) {
+        k[j] += base;
+        pr[j] = WHOLE || (uint32_t)(kChPer * lane + j) < nval ? pr[j] * xv[j] : 0.f;
+    }
+    // the lane's last run, summed across the lanes it covers (lanes with the same last run: its first lane, then lanes without a start)
+    float t = pr[0];
+#pragma unroll
+    for (int j = 1; j < kChPer; j++) t = st[j] ? pr[j] : t + pr[j];
+    const float run = wave_run_sum(t, k[kChPer - 1]);
+    const float left = dpp_val<0x138>(0.f, run);                // wave_shr:1
+    const uint32_t st_right = dpp_u32<0x130>(1u, st[0]);        // wave_shl:1; the last position of the chunk ends its run
+    __builtin_amdgcn_wave_barrier();                            // every lane has read its values: the staging area becomes T
+    const uint32_t dump = kChV + (uint32_t)lane;
+    float acc = st[0] ? pr[0] : left + pr[0];                   // positions before the lane's first start continue the left lane's run
+#pragma unroll
+    for (int j = 1; j < kChPer; j++) {
+        T[st[j] ? (k[j - 1] & (kChV - 1u)) : dump] = acc;
+        acc = st[j] ? pr[j] : acc + pr[j];
+    }
+    T[st_right ? (k[kChPer - 1] & (kChV - 1u)) : dump] = acc;
+}
+
+template <bool SORTED>
 __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__restrict__ recs, const uint32_t *__restrict__ words,
                                                             const float *__restrict__ values, const float *__restrict__ x, float *__restrict__ y,
                                                             float *__restrict__ carry, uint32_t *__restrict__ counters, uint32_t nnz,
@@ -1248,65 +1356,75 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
 {
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    __shared__ __attribute__((aligned(16))) float win[kChWin];
+    __shared__ __attribute__((aligned(16))) float win[SORTED ? kChSortedLds : kChWin];
     const int lane = lane_id();
     const uint32_t c = blockIdx.x;
     const ChunkRec rc = recs[c];
-    const uint32_t first = c * kChV + (uint32_t)(kChPer * lane);
-    const rsrc_t rw = make_rsrc(words, nnz * 4u), rv = make_rsrc(values, nnz * 4u), rx = make_rsrc(x, num_cols * 4u);
-    uint32_t w[kChPer];
-    float a[kChPer], xv[kChPer];
-    if (c * kChV + kChV <= nnz) {  // a whole chunk: 16-byte loads
-#pragma unroll
-        for (int q = 0; q < kChPer; q += 4) {
-            const u4 wq = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rw, (first + q) * 4u, 0, 0));
-            const f4 aq = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (first + q) * 4u, 0, 0));
-#pragma unroll
-            for (int i = 0; i < 4; i++) { w[q + i] = wq[i]; a[q + i] = aq[i]; }
-        }
-    } else {  // the last chunk: element loads, values past nnz read 0
-#pragma unroll
-        for (int j = 0; j < kChPer; j++) {
-            const uint32_t off = first + j < nnz ? (first + j) * 4u : kOob;
-            w[j] = __builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0);
-            a[j] = Buf<float>::ld(rv, off);
-        }
-    }
-    const uint32_t cmask = (1u << colbits) - 1u;
-#pragma unroll
-    for (int j = 0; j < kChPer; j++) xv[j] = Buf<float>::ld(rx, first + j < nnz ? (w[j] & cmask) * 4u : kOob);
-
-    float pr[kChPer];
-    uint32_t rr[kChPer];
-#pragma unroll
-    for (int j = 0; j < kChPer; j++) {
-        rr[j] = first + j < nnz ? w[j] >> colbits : rc.nwin - 8u;  // past nnz (last chunk only): the last block-row, adding 0
-        pr[j] = first + j < nnz ? a[j] * xv[j] : 0.f;
-    }
-    if (rc.nwin == 8) {
-        // one block-row: eight register sums per lane
-        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < kChPer; j++) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) s[k] += rr[j] == (uint32_t)k ? pr[j] : 0.f;
-        }
-        const float v = chunk_sum8(s, lane);
-        if ((lane & 7) == 0) win[((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1)] = v;
+    if constexpr (SORTED) {
+        if (c * kChV + kChV <= nnz) chunk_sorted_reduce<true>(win, words, values, x, c, nnz, num_cols, colbits, lane);
+        else chunk_sorted_reduce<false>(win, words, values, x, c, nnz, num_cols, colbits, lane);
     } else {
-        for (uint32_t e = (uint32_t)lane; e < rc.nwin; e += 64) win[e] = 0.f;
-        __builtin_amdgcn_wave_barrier();
-        chunk_seg_reduce(win, rr, pr);
+        const uint32_t first = c * kChV + (uint32_t)(kChPer * lane);
+        const rsrc_t rw = make_rsrc(words, nnz * 4u), rv = make_rsrc(values, nnz * 4u), rx = make_rsrc(x, num_cols * 4u);
+        uint32_t w[kChPer];
+        float a[kChPer], xv[kChPer];
+        if (c * kChV + kChV <= nnz) {  // a whole chunk: 16-byte loads
+#pragma unroll
+            for (int q = 0; q < kChPer; q += 4) {
+                const u4 wq = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rw, (first + q) * 4u, 0, 0));
+                const f4 aq = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rv, (first + q) * 4u, 0, 0));
+#pragma unroll
+                for (int i = 0; i < 4; i++) { w[q + i] = wq[i]; a[q + i] = aq[i]; }
+            }
+        } else {  // the last chunk: element loads, values past nnz read 0
+#pragma unroll
+            for (int j = 0; j < kChPer; j++) {
+                const uint32_t off = first + j < nnz ? (first + j) * 4u : kOob;
+                w[j] = __builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0);
+                a[j] = Buf<float>::ld(rv, off);
+            }
+        }
+        const uint32_t cmask = (1u << colbits) - 1u;
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) xv[j] = Buf<float>::ld(rx, first + j < nnz ? (w[j] & cmask) * 4u : kOob);
+
+        float pr[kChPer];
+        uint32_t rr[kChPer];
+#pragma unroll
+        for (int j = 0; j < kChPer; j++) {
+            rr[j] = first + j < nnz ? w[j] >> colbits : rc.nwin - 8u;  // past nnz (last chunk only): the last block-row, adding 0
+            pr[j] = first + j < nnz ? a[j] * xv[j] : 0.f;
+        }
+        if (rc.nwin == 8) {
+            // one block-row: eight register sums per lane
+            float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < kChPer; j++) {
+#pragma unroll
+                for (int k = 0; k < 8; k++) s[k] += rr[j] == (uint32_t)k ? pr[j] : 0.f;
+            }
+            const float v = chunk_sum8(s, lane);
+            if ((lane & 7) == 0) win[((lane >> 5) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 3) & 1)] = v;
+        } else {
+            for (uint32_t e = (uint32_t)lane; e < rc.nwin; e += 64) win[e] = 0.f;
+            __builtin_amdgcn_wave_barrier();
+            chunk_seg_reduce(win, rr, pr);
+        }
     }
     __builtin_amdgcn_wave_barrier();
+    // the sum of row `rel` of the window (rel < nwin)
+    const auto row_sum = [&](uint32_t rel) -> float {
+        if constexpr (SORTED) return chunk_row_value(win, (const uint32_t *)(win + kChT), (const uint32_t *)(win + kChT) + 32, rel);
+        else return win[rel];
+    };
     // folded block-rows: park the 8 partial sums, drain them, then take both tickets with ONE returning atomic -- lanes 0 (head) and 1
     // (tail) at lane-dependent addresses; two uniform-address atomics were each rewritten into a wave-reduced atomic and waited for in
     // turn (round 8).  The own-row y stores go out behind the ticket and overlap its round trip.
     uint32_t ticket = 0;
     if (rc.flags) {
-        if ((rc.flags & kChHead) && lane < 8) __hip_atomic_store(&carry[((size_t)c * 2) * 8 + lane], win[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((rc.flags & kChHead) && lane < 8) __hip_atomic_store(&carry[((size_t)c * 2) * 8 + lane], row_sum((uint32_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((rc.flags & kChTail) && lane < 8)
-            __hip_atomic_store(&carry[((size_t)c * 2 + 1) * 8 + lane], win[rc.nwin - 8u + (uint32_t)lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&carry[((size_t)c * 2 + 1) * 8 + lane], row_sum(rc.nwin - 8u + (uint32_t)lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0 ? (rc.flags & kChHead) != 0u : lane == 1 && (rc.flags & kChTail) != 0u)
             ticket = __hip_atomic_fetch_add(&counters[lane == 0 ? rc.head_ca : c], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1316,7 +1434,13 @@ __global__ __launch_bounds__(64, 8) void spmv_chunk_kernel(const ChunkRec *__res
     const uint32_t row_end = min(rc.own_e * 8u, num_rows);
     for (uint32_t row = rc.own_b * 8u + (uint32_t)lane; row < row_end; row += 64) {
         const int32_t rel = (int32_t)row - base;
-        y[row] = rel >= 0 && rel < (int32_t)rc.nwin ? win[rel] : 0.f;
+        const bool in = rel >= 0 && rel < (int32_t)rc.nwin;
+        if constexpr (SORTED) {
+            const float v = row_sum(in ? (uint32_t)rel : 0u);
+            y[row] = in ? v : 0.f;
+        } else {
+            y[row] = in ? win[rel] : 0.f;
+        }
     }
     if (!rc.flags) return;
     const uint32_t th = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 0), tt = (uint32_t)__builtin_amdgcn_readlane((int)ticket, 1);
@@ -1359,6 +1483,37 @@ __global__ void chunk_words_kernel(const uint64_t *__restrict__ keys, const uint
     }
 }
 
+// pass 3 (row-sorted form only), one workgroup per chunk, in place: the round-7 words {relative row, column} in storage order become the
+// row-ordered words of layout 2.  A value's position is the number of the chunk's values with a smaller (row, storage index) -- counted,
+// not ranked by atomics, so the same structure always gives the same words (the bitmap is an OR: order-free).
+__global__ __launch_bounds__(kChV) void chunk_sort_kernel(uint32_t *__restrict__ words, uint32_t nnz, uint32_t colbits)
+{
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) uint32_t keys[kChV];
+    __shared__ uint32_t out[kChV], srow[kChV], bm[kChWin / 32];
+    const uint32_t c = blockIdx.x, i = threadIdx.x, n = min(nnz - c * kChV, kChV);
+    const uint32_t w = words[(size_t)c * kChV + i];
+    const uint32_t r = w >> colbits, key = i < n ? (r << 9) | i : ~0u;  // r < kChWin: 19 bits; the padding sorts last
+    keys[i] = key;
+    out[i] = 0;
+    srow[i] = ~0u;
+    if (i < kChWin / 32) bm[i] = 0;
+    __syncthreads();
+    if (i < n) {
+        uint32_t pos = 0;
+        for (uint32_t j = 0; j < kChV / 4; j++) {
+            const u4 q = ((const u4 *)keys)[j];
+            pos += (q[0] < key ? 1u : 0u) + (q[1] < key ? 1u : 0u) + (q[2] < key ? 1u : 0u) + (q[3] < key ? 1u : 0u);
+        }
+        out[pos] = (w & ((1u << colbits) - 1u)) | (i << colbits);
+        srow[pos] = r;
+        atomicOr(&bm[(r >> 5) & (kChWin / 32 - 1)], 1u << (r & 31u));
+    }
+    __syncthreads();
+    const uint32_t start = i < n && (i == 0 || srow[i] != srow[i - 1]) ? 1u : 0u;
+    words[(size_t)c * kChV + i] = out[i] | (start << (colbits + 9u)) | (((bm[i >> 4] >> ((2u * i) & 31u)) & 3u) << (colbits + 10u));
+}
+
 // the chunked sweep's cache: built once per matrix (bmsp_matrix_prepare or the first sweep); nothing is kept for a matrix it does not fit
 void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
 {
@@ -1370,6 +1525,9 @@ void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
     const uint32_t nch = (nnz + kChV - 1) / kChV;
     const int colbits = A->num_cols <= 1 ? 1 : 32 - __builtin_clz((uint32_t)A->num_cols - 1u);
     if (colbits > 28) return;
+    // the row-sorted words need 9 bits of storage index, the start bit and 2 bitmap bits above the column (BMSP_SPMV_CHUNK_SORTED=0: round 7)
+    const char *se = getenv("BMSP_SPMV_CHUNK_SORTED");
+    const bool sorted = kChV == 512 && kChWin == 1024 && colbits <= kChSortedColbits && !(se && atoi(se) == 0);
     std::vector<uint32_t> fb(nch), lb(nch);
     {
         DevBuf<uint32_t> d(2 * (size_t)nch);
@@ -1415,9 +1573,14 @@ void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
         BMSP_HIP(hipMemcpyAsync(d.p, fb.data(), 4 * (size_t)nch, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(chunk_words_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, A->keys, A->bmps, A->offsets, nb, d.p, (uint32_t)colbits, (uint32_t *)mem);
         BMSP_CHECK_LAUNCH();
+        if (sorted) {
+            hipLaunchKernelGGL(chunk_sort_kernel, dim3(nch), dim3(kChV), 0, st, (uint32_t *)mem, nnz, (uint32_t)colbits);
+            BMSP_CHECK_LAUNCH();
+        }
         BMSP_HIP(hipStreamSynchronize(st));  // the host records and the staging buffer go away with this scope
     }
     A->spmv_cw = (uint32_t *)mem;
+    A->spmv_cw_layout = sorted ? 2 : 1;
     A->spmv_cw_chunks = nch;
     A->spmv_cw_split = split;
     A->spmv_cw_off_rec = off_rec; A->spmv_cw_off_cnt = off_cnt; A->spmv_cw_off_carry = off_carry;
@@ -1479,7 +1642,7 @@ void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t s
                 build_chunk_cache(A, st);
                 if (A->spmv_cw) {
                     const char *cm = (const char *)A->spmv_cw;
-                    hipLaunchKernelGGL(spmv_chunk_kernel, dim3((uint32_t)A->spmv_cw_chunks), dim3(64), 0, st, (const ChunkRec *)(cm + A->spmv_cw_off_rec),
+                    hipLaunchKernelGGL(A->spmv_cw_layout == 2 ? spmv_chunk_kernel<true> : spmv_chunk_kernel<false>, dim3((uint32_t)A->spmv_cw_chunks), dim3(64), 0, st, (const ChunkRec *)(cm + A->spmv_cw_off_rec),
                                        (const uint32_t *)cm, (const float *)A->values, (const float *)v, (float *)u, (float *)(cm + A->spmv_cw_off_carry),
                                        (uint32_t *)(cm + A->spmv_cw_off_cnt), (uint32_t)A->nnz, (uint32_t)A->num_rows, (uint32_t)A->num_cols,
                                        (uint32_t)A->spmv_cw_colbits);
@@ -1591,6 +1754,15 @@ void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kerne
     }
     if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", name);
     if (compulsory) *compulsory = bytes;
+}
+
+// the layout of the chunk cache the sweep of A would read (built as spmv_launch_info builds it): 0 = no chunk cache (another kernel takes
+// A), 1 = words in storage order (round 7), 2 = row-sorted words
+int spmv_chunk_layout(bmsp_matrix_s *A, hipStream_t st)
+{
+    char name[64];
+    spmv_launch_info(A, BMSP_SPMV_DEFAULT, st, name, sizeof(name), nullptr, nullptr);
+    return strcmp(name, "spmv_chunk_kernel") == 0 ? A->spmv_cw_layout : 0;
 }
 
 void prepare_spmv(bmsp_matrix_s *A, hipStream_t st)

@@ -34,7 +34,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -135,6 +135,7 @@ def lib():
         L.bmsp_spmv.argtypes = [vp, vp, vp, i, vp]
         L.bmsp_spmm.argtypes = [vp, vp, i64, vp, i64, i, vp]
         L.bmsp_spmv_launch_info.argtypes = [vp, i, C.c_char_p, C.c_size_t, p(i64), p(i64)]
+        L.bmsp_spmv_chunk_layout.argtypes = [vp, p(i)]
         L.bmsp_spmm_launch_info.argtypes = [vp, i, i64, i64, C.c_char_p, C.c_size_t]
         L.bmsp_spgemm.argtypes = [vp, vp, p(vp), i, i, i, vp, p(SpgemmStats)]
         L.bmsp_spgemm_symbolic.argtypes = [vp, vp, p(vp), i, i, vp, p(SpgemmStats)]
@@ -588,6 +589,13 @@ def spmv_launch_info(A, variant=0):
     cb, fb = C.c_int64(), C.c_int64()
     check(lib().bmsp_spmv_launch_info(A.h, int(variant), name, 128, C.byref(cb), C.byref(fb)))
     return {"kernel": name.value.decode(), "compulsory_bytes": cb.value, "format_bytes": fb.value}
+
+
+def spmv_chunk_layout(A):
+    """layout of the chunked sweep's cache for A: 0 = the sweep does not take spmv_chunk_kernel, 1 = storage order, 2 = row-sorted."""
+    out = C.c_int()
+    check(lib().bmsp_spmv_chunk_layout(A.h, C.byref(out)))
+    return out.value
 
 
 def spmm(A, X, k, Y=None, ldx=None, ldy=None, stream=None):

@@ -288,6 +288,12 @@ int bmsp_spmv(bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *st
  * block-row pointer + x + y.  Reporting only: no reference line to replace (the reference prints a time, src/bmSparse_SPMV.cu:306). */
 int bmsp_spmv_launch_info(bmsp_matrix_t A, int variant, char *kernel_name, size_t kernel_name_cap, int64_t *compulsory_bytes, int64_t *format_bytes);
 
+/* The layout of the chunked sweep's structure cache for A (spmv_chunk_kernel; the cache is built if it is not yet, as
+ * bmsp_spmv_launch_info builds it): *layout = 0 when the default sweep of A does not take the chunked kernel, 1 = one word {row, column}
+ * per stored value in storage order, 2 = the row-sorted words (up to 2^20 columns; BMSP_SPMV_CHUNK_SORTED=0 keeps layout 1).  Both move
+ * the same bytes.  Reporting only. */
+int bmsp_spmv_chunk_layout(bmsp_matrix_t A, int *layout);
+
 /* SURVEY 8(f)3 -- Y = A * X for k vectors at once (what the reference's unfinished `batched` path points at,
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
