@@ -405,8 +405,18 @@ void free_matrix(bmsp_matrix_s *m)
     pool_free(m->sp_tasks); pool_free(m->sp_task_begin); pool_free(m->sp_c_of_wave);
     pool_free(m->tp_map);
     pool_free(m->add_map);
+    drop_spmv_op_views(m);
     free_matrix(m->shard_view);
     delete m;
+}
+
+void drop_spmv_op_views(bmsp_matrix_s *m)
+{
+    for (bmsp_spmv_op_view &w : m->spmv_op_views) {
+        pool_free(w.mem);
+        w = bmsp_spmv_op_view();
+    }
+    pool_free(m->spmv_op_tmp); m->spmv_op_tmp = nullptr;
 }
 
 void alloc_tile_arrays(bmsp_matrix_s *m, uint64_t nb)
@@ -456,6 +466,7 @@ void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)
     pool_free(m->col_mass); m->col_mass = nullptr;
     pool_free(m->tp_map); m->tp_map = nullptr; m->tp_src_uid = 0; m->tp_permute = 0;
     pool_free(m->add_map); m->add_map = nullptr; m->add_a_uid = 0; m->add_b_uid = 0;
+    drop_spmv_op_views(m);
     free_matrix(m->shard_view); m->shard_view = nullptr; m->shard_world = 0; m->shard_rank = 0; m->shard_bounds.clear();
 }
 

@@ -598,6 +598,34 @@ int bmsp_spmv_chunk_layout(bmsp_matrix_t A, int *layout)
     BMSP_API_END
 }
 
+int bmsp_spmv_op(bmsp_matrix_t A, int op, double alpha, const void *d_v, double beta, void *d_u, void *stream)
+{
+    BMSP_API_BEGIN
+    spmv_op_check_op(op);
+    need(A, "matrix A"); need(d_v, "d_v"); need(d_u, "d_u");
+    load_kernels();
+    spmv_op(A, op, alpha, d_v, beta, d_u, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spmv_op_launch_info(bmsp_matrix_t A, int op, bmsp_spmv_op_info *info)
+{
+    BMSP_API_BEGIN
+    spmv_op_check_op(op);
+    need(A, "matrix A"); need(info, "info");
+    load_kernels();
+    spmv_op_launch_info(A, op, nullptr, info);
+    BMSP_API_END
+}
+
+int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
+                            int64_t *split_blocks, int64_t *slots)
+{
+    BMSP_API_BEGIN
+    spmv_op_plan_items(ptr, blocks, split, items, folds, n_items, split_blocks, slots);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

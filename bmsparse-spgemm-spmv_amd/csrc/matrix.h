@@ -9,6 +9,16 @@
 
 namespace bmsp { uint64_t next_matrix_uid(); }
 
+// The cached view of bmsp_spmv_op for one op (spmv_op.hip): the tiles as 16-byte records {bitmap lo, hi, value offset, the tile's OTHER
+// block index} in the order the sweep walks them, the pointer of blocks + 1 entries per output block (op T; op N uses rowptr), the work
+// items {output block, first tile, end tile, scratch slot or ~0u}, the fold list {output block, first slot, parts} of the split blocks and
+// 8 accumulators of scratch per slot -- one allocation, structure only (kept across value-only invalidation).
+struct bmsp_spmv_op_view {
+    uint32_t *mem = nullptr;
+    size_t off_ptr = 0, off_items = 0, off_folds = 0, off_scratch = 0, bytes = 0;
+    int64_t blocks = 0, items = 0, split_blocks = 0, slots = 0;
+};
+
 struct bmsp_matrix_s {
     // identity of this matrix's STRUCTURE: a fresh number at construction and after bmsp_matrix_invalidate(m, 1).  What one matrix remembers
     // about another (the row-merge hint below) is keyed by it -- not by a device pointer, which the pool hands out again
@@ -85,6 +95,9 @@ struct bmsp_matrix_s {
     uint64_t struct_hash = 0;  // this matrix: sum over its blocks of mix(key, bitmap), + dimensions; 0 = not computed (ensure_struct_hash)
     int values_finite = -1;
     int f32_exp_min = 255, f32_exp_max = 0;  // fp32: biased exponent range of the non-zero stored values (with values_finite)       // fp16 operands of the strip block-MAC: 1 = no inf / NaN stored (-1 = not looked yet)
+    // bmsp_spmv_op: the view per op (0 = N, 1 = T), built on first use; the sum of a layout-0 matrix under op N before its epilogue
+    bmsp_spmv_op_view spmv_op_views[2];
+    void *spmv_op_tmp = nullptr;
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -203,6 +216,17 @@ void check_layout_flag(int value, const char *name);
 void refuse_view(const bmsp_matrix_s *m, const char *op);
 // before m's values are rewritten in place: drops what invalidate_matrix(m, 0) drops
 void drop_value_caches(bmsp_matrix_s *m);
+// transpose.hip: the tiles of a matrix in (block-column, block-row) order -- the sorted swapped keys and, as payload, the source tile of
+// each.  The four buffers live as long as the struct (the pool is not stream-aware); take_* hands the two results to a matrix.
+struct TileSort {
+    DevBuf<uint64_t> k0, k1;
+    DevBuf<uint32_t> p0, p1;
+    const uint64_t *keys = nullptr;
+    const uint32_t *map = nullptr;
+    uint64_t *take_keys() { return keys == k0.p ? k0.take() : k1.take(); }
+    uint32_t *take_map() { return map == p0.p ? p0.take() : p1.take(); }
+};
+void sort_tiles_by_block_column(const bmsp_matrix_s *A, TileSort &ts, hipStream_t st);
 // transpose.hip: out = A^T (swap) or A (!swap) with tiles in layout out_transposed; re-gather such an out's values from A
 bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st);
 void copy_values_from(bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
@@ -229,6 +253,13 @@ void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);
 void spmv(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t st, int64_t row_lo = 0, int64_t row_hi = -1);
 void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kernel, size_t kernel_cap, int64_t *compulsory, int64_t *format_bytes);
 int spmv_chunk_layout(bmsp_matrix_s *A, hipStream_t st);
+// spmv_op.hip: u = alpha * op(A) * v + beta * u for either tile layout; what that call launches; the host part of its item planner
+void spmv_op_check_op(int op);
+void spmv_op(bmsp_matrix_s *A, int op, double alpha, const void *v, double beta, void *u, hipStream_t st);
+void spmv_op_launch_info(bmsp_matrix_s *A, int op, hipStream_t st, bmsp_spmv_op_info *info);
+void spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
+                        int64_t *split_blocks, int64_t *slots);
+void drop_spmv_op_views(bmsp_matrix_s *m);
 void spmm(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st);
 void spmm_launch_info(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStream_t st, char *kernel, size_t kernel_cap);
 void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **C, int mode, int tc_version, int verbose, hipStream_t st,

@@ -123,6 +123,20 @@ void check_source(const bmsp_matrix_s *A, int out_transposed, const char *what)
 
 }  // namespace
 
+// Every tile of A as (swapped key (bcol, brow), tile index), stably sorted on the block-column bits only: the input is sorted by
+// (brow, bcol), so equal block columns keep their block-row order and the result is in (bcol, brow) order.
+void sort_tiles_by_block_column(const bmsp_matrix_s *A, TileSort &ts, hipStream_t st)
+{
+    const uint64_t nb = (uint64_t)A->block_num;
+    ts.k0.alloc(nb); ts.k1.alloc(nb); ts.p0.alloc(nb); ts.p1.alloc(nb);
+    device_for_each(SwappedKey{A->keys, ts.k0.p, ts.p0.p}, nb, st);
+    PingPong<uint64_t> kk{ts.k0.p, ts.k1.p};
+    PingPong<uint32_t> pp{ts.p0.p, ts.p1.p};
+    const int cbits = ceil_log2_u64((uint64_t)A->num_block_cols());
+    device_radix_sort_pairs<uint32_t>(kk, pp, nb, 32, 32 + cbits, st);
+    ts.keys = kk.cur; ts.map = pp.cur;
+}
+
 // out = A^T (swap = true) or A (swap = false) with its tiles in layout out_transposed
 bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st)
 {
@@ -135,17 +149,11 @@ bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap,
     // a transpose into the other layout, or a conversion into the same one, keeps every tile as it is
     m->tp_permute = (out_transposed != A->transposed) != swap ? 1 : 0;
     const uint64_t nb = (uint64_t)A->block_num;
-    DevBuf<uint64_t> k0, k1;  // sort temporaries: go back to the pool after the synchronisation at the end
-    DevBuf<uint32_t> p0, p1;
+    TileSort ts;  // sort temporaries: go back to the pool after the synchronisation at the end
     if (swap) {
-        k0.alloc(nb); k1.alloc(nb); p0.alloc(nb); p1.alloc(nb);
-        device_for_each(SwappedKey{A->keys, k0.p, p0.p}, nb, st);
-        PingPong<uint64_t> kk{k0.p, k1.p};
-        PingPong<uint32_t> pp{p0.p, p1.p};
-        const int cbits = ceil_log2_u64((uint64_t)A->num_block_cols());
-        device_radix_sort_pairs<uint32_t>(kk, pp, nb, 32, 32 + cbits, st);  // stable: equal block columns keep their block-row order
-        m->keys = kk.cur == k0.p ? k0.take() : k1.take();
-        m->tp_map = pp.cur == p0.p ? p0.take() : p1.take();
+        sort_tiles_by_block_column(A, ts, st);
+        m->keys = ts.take_keys();
+        m->tp_map = ts.take_map();
     }
     alloc_tile_arrays(m.get(), nb);  // (a transpose holds its keys already)
     alloc_values(m.get(), m->nnz);

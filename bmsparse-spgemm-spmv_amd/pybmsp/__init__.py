@@ -22,6 +22,8 @@ SPMV_DEFAULT, SPMV_BATCHED = 0, 1
 PRUNE_ABS, PRUNE_ROW_REL = 0, 1
 PRUNE_KEEP_DIAGONAL = 1
 SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
+OP_N, OP_T = 0, 1
+_OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
 # every symbol include/bmsp.h declares (checked by tests/test_abi.py against the header text)
@@ -34,7 +36,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -65,6 +67,16 @@ class PruneStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SpmvOpInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("slots", C.c_int), ("items", C.c_int64), ("split_blocks", C.c_int64), ("view_bytes", C.c_int64),
+                ("compulsory_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
 
 
 class ShardStats(C.Structure):
@@ -136,6 +148,9 @@ def lib():
         L.bmsp_spmm.argtypes = [vp, vp, i64, vp, i64, i, vp]
         L.bmsp_spmv_launch_info.argtypes = [vp, i, C.c_char_p, C.c_size_t, p(i64), p(i64)]
         L.bmsp_spmv_chunk_layout.argtypes = [vp, p(i)]
+        L.bmsp_spmv_op.argtypes = [vp, i, C.c_double, vp, C.c_double, vp, vp]
+        L.bmsp_spmv_op_launch_info.argtypes = [vp, i, p(SpmvOpInfo)]
+        L.bmsp_spmv_op_plan_items.argtypes = [vp, i64, i64, vp, vp, p(i64), p(i64), p(i64)]
         L.bmsp_spmm_launch_info.argtypes = [vp, i, i64, i64, C.c_char_p, C.c_size_t]
         L.bmsp_spgemm.argtypes = [vp, vp, p(vp), i, i, i, vp, p(SpgemmStats)]
         L.bmsp_spgemm_symbolic.argtypes = [vp, vp, p(vp), i, i, vp, p(SpgemmStats)]
@@ -411,6 +426,14 @@ class BmSpMatrix:
         """the matrix with d[i] stored at every (i, i): pybmsp.from_diagonal"""
         return from_diagonal(d, num_rows, num_cols, dtype, transposed, stream)
 
+    def matvec(self, v, alpha=1.0, beta=0.0, u=None, stream=None):
+        """alpha * this * v + beta * u, whatever the tile layout: pybmsp.spmv_op(op="N")"""
+        return spmv_op(self, v, "N", alpha, beta, u, stream)
+
+    def rmatvec(self, v, alpha=1.0, beta=0.0, u=None, stream=None):
+        """alpha * this^T * v + beta * u without a transposed copy: pybmsp.spmv_op(op="T")"""
+        return spmv_op(self, v, "T", alpha, beta, u, stream)
+
     def copy_values_from(self, src, stream=None):
         """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
         check(lib().bmsp_matrix_copy_values(src.h, self.h, stream))
@@ -589,6 +612,53 @@ def spmv_launch_info(A, variant=0):
     cb, fb = C.c_int64(), C.c_int64()
     check(lib().bmsp_spmv_launch_info(A.h, int(variant), name, 128, C.byref(cb), C.byref(fb)))
     return {"kernel": name.value.decode(), "compulsory_bytes": cb.value, "format_bytes": fb.value}
+
+
+def _op(op):
+    if op not in _OPS:
+        raise ValueError("op must be 'N' or 'T' (got %r)" % (op,))
+    return _OPS[op]
+
+
+def spmv_op(A, v, op="N", alpha=1.0, beta=0.0, u=None, stream=None):
+    """u = alpha * op(A) * v + beta * u (bmsp_spmv_op), op "N" or "T", A in either tile layout.  v: DeviceArray of A's dtype with num_cols
+    ("N") / num_rows ("T") entries; u: DeviceArray (float32, float64 for F64) of the output length, made when None (beta must then be 0).
+    Returns u.  Asynchronous on `stream` once the cached view of (A, op) exists."""
+    o = _op(op)
+    i = A.info()
+    n_in, n_out = (i["num_rows"], i["num_cols"]) if o == OP_T else (i["num_cols"], i["num_rows"])
+    if v.dtype != np.dtype(NP_DTYPE[i["dtype"]]) or v.n < n_in:
+        raise ValueError("v must hold %d entries of %s" % (n_in, np.dtype(NP_DTYPE[i["dtype"]]).name))
+    if u is None:
+        if beta != 0:
+            raise ValueError("beta != 0 needs u")
+        u = DeviceArray(n_out, OUT_DTYPE[i["dtype"]])
+    elif u.dtype != np.dtype(OUT_DTYPE[i["dtype"]]) or u.n < n_out:
+        raise ValueError("u must hold %d entries of %s" % (n_out, np.dtype(OUT_DTYPE[i["dtype"]]).name))
+    check(lib().bmsp_spmv_op(A.h, o, float(alpha), v.ptr, float(beta), u.ptr, stream))
+    return u
+
+
+def spmv_op_launch_info(A, op):
+    """{"kernel", "slots", "items", "split_blocks", "view_bytes", "compulsory_bytes"} of the launch spmv_op(A, v, op) makes; builds the
+    cached view of (A, op) if it is missing (bmsp_spmv_op_launch_info)."""
+    o = _op(op)
+    info = SpmvOpInfo()
+    check(lib().bmsp_spmv_op_launch_info(A.h, o, C.byref(info)))
+    return info.as_dict()
+
+
+def spmv_op_plan_items(ptr, split):
+    """(items [n, 4], folds [split blocks, 3], scratch slots) of the view's item planner for a block pointer (host arithmetic of
+    spmv_op.hip; bmsp_spmv_op_plan_items)."""
+    pt = np.ascontiguousarray(ptr, dtype=np.uint32)
+    blocks = max(0, pt.size - 1)
+    ni, nf, ns = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib().bmsp_spmv_op_plan_items(pt.ctypes.data, blocks, int(split), None, None, C.byref(ni), C.byref(nf), C.byref(ns)))
+    items, folds = np.zeros((ni.value, 4), np.uint32), np.zeros((nf.value, 3), np.uint32)
+    check(lib().bmsp_spmv_op_plan_items(pt.ctypes.data, blocks, int(split), items.ctypes.data, folds.ctypes.data, C.byref(ni), C.byref(nf),
+                                        C.byref(ns)))
+    return items, folds, ns.value
 
 
 def spmv_chunk_layout(A):

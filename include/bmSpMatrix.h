@@ -289,6 +289,16 @@ template <class ValueIn, class ValueOut> inline void bmSparse_SpMV(bmSpMatrix<Va
     bmsp::check(bmsp_synchronize());
 }
 
+/* u = alpha * op(A) * v + beta * u (bmsp_spmv_op), op = BMSP_OP_N or BMSP_OP_T, A in either tile layout: the transposed product without a
+ * transposed copy.  v (the input length of op(A), A's value type) and u (the output length; float, double for double) are device pointers;
+ * synchronous like bmSparse_SpMV. */
+template <class ValueIn>
+inline void bmSparse_SpMV_op(bmSpMatrix<ValueIn> &A, int op, double alpha, const ValueIn *v, double beta, typename bmsp::vector_of<ValueIn>::type *u)
+{
+    bmsp::check(bmsp_spmv_op(A.handle(), op, alpha, v, beta, u, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+
 /* Multi-vector form: U = A * V for k vectors, V row-major num_cols x k, U row-major num_rows x k. */
 template <class ValueIn, class ValueOut> inline void bmSparse_SpMM(bmSpMatrix<ValueIn> &A, ValueIn *V, ValueOut *U, int k)
 {

@@ -294,6 +294,49 @@ int bmsp_spmv_launch_info(bmsp_matrix_t A, int variant, char *kernel_name, size_
  * the same bytes.  Reporting only. */
 int bmsp_spmv_chunk_layout(bmsp_matrix_t A, int *layout);
 
+/* u = alpha * op(A) * v + beta * u, op(A) = A (BMSP_OP_N) or A^T (BMSP_OP_T), for a matrix in EITHER tile layout -- without
+ * bmsp_matrix_transpose / bmsp_matrix_convert_layout, a second copy of the matrix or a second set of SpMV caches.  Nothing in the reference
+ * is replaced: its one product is u = A * v on a row-major A (src/bmSparse_SPMV.cu:191-230; bmsp_spmv above).
+ *   Vectors: v has the input length of op(A) (num_cols for N, num_rows for T), elements of A's dtype (fp16 for F16), as bmsp_spmv's v;
+ *       u has the output length, float for F32 / F16 and double for F64.  Matrix coordinates, whatever the tile layout.
+ *   Sum: t_j = the sum over the stored entries of row j of op(A) of a * v, products and sums in fp32 (double for F64), F16 operands widened
+ *       exactly; +0 for a row without stored entries.  The order of summation is the implementation's, but t is a pure function of A's
+ *       arrays, v and the two switches below: no floating-point atomic anywhere, no dependence on scheduling, two calls with the same
+ *       inputs give the same bits.
+ *   Epilogue: alpha and beta are rounded once to the vector type.  beta == 0 (after that rounding): u_j = fl(alpha * t_j); u is not read,
+ *       a NaN in it does not propagate.  Otherwise u_j = fl(fl(alpha * t_j) + fl(beta * u_j)), each operation rounded on its own, never
+ *       contracted (as bmsp_matrix_add).  alpha == 0 is not special-cased.  Every entry of u is written.
+ *   (N, row-major A) is bmsp_spmv's case: t is exactly what bmsp_spmv(A, v, ., BMSP_SPMV_DEFAULT) writes; with alpha == 1 and beta == 0
+ *       the call IS that call, otherwise bmsp_spmv runs into a temporary kept on the handle and one epilogue kernel follows.
+ *   The other three cases sweep a cached view, one per op, built on first use (structure only: 16 B per tile -- bitmap, value offset, the
+ *       tile's other block index -- in the order of the output blocks, A's own for N, (block-column, block-row) for T; 16 B per work
+ *       item; 8 accumulators of scratch per item of an output block of more than SPLIT tiles).  Values are read from A's value array at
+ *       every call, so a value-only update in place needs no bmsp_matrix_invalidate (as for bmsp_spmv).  The view is dropped by
+ *       bmsp_matrix_invalidate(A, 1) and bmsp_matrix_free; bmsp_matrix_invalidate(A, 0), bmsp_matrix_copy_values, _scale_values and
+ *       _add_values into A keep it.  bmsp_matrix_prepare does not build it.
+ *   Asynchronous on `stream`, except for the one-time build of the view (it synchronises).  A's four arrays are not modified.  One stream
+ *       per handle at a time (the scratch and the temporary live on the handle).
+ *   Switches: BMSP_SPMV_OP_SLOTS=1/8, read per call (lane groups of a wave that walk one work item; default 8 from a mean of 6 tiles per
+ *       output block); BMSP_SPMV_OP_SPLIT=<tiles>, read when a view is built (default 64).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles: op not 0 / 1; null A, d_v, d_u, info;
+ *   row-panel views.  BMSP_ERR_LIMIT: 2^32 tiles or values or more. */
+#define BMSP_OP_N 0
+#define BMSP_OP_T 1
+int bmsp_spmv_op(bmsp_matrix_t A, int op, double alpha, const void *d_v, double beta, void *d_u, void *stream);
+/* What bmsp_spmv_op(A, op, ...) launches -- the launcher's own decisions, for tests to pin: the sweep kernel by name
+ * ("spmv_op_sweep_kernel<MINOR, 8>": MAJOR / MINOR = the output index is the byte / the bit index of the bitmap; "bmsp_spmv: <kernel>" for
+ * (N, row-major A), which has no view: slots, items, split_blocks 0), the lane groups per item (1 / 8), the work items, the output blocks
+ * split into several items, the bytes the view holds and the bytes the launch moves (records, values, items, v, u, scratch stored and read
+ * back, fold list; bmsp_spmv_launch_info's figure for bmsp_spmv).  Builds the view if it is missing.  Reporting only. */
+typedef struct { char kernel[64]; int slots; int64_t items, split_blocks, view_bytes, compulsory_bytes; } bmsp_spmv_op_info;
+int bmsp_spmv_op_launch_info(bmsp_matrix_t A, int op, bmsp_spmv_op_info *info);
+/* The item planner of the view, host only (no GPU call): over `blocks` output blocks with tiles [ptr[b], ptr[b + 1]), a block of at most
+ * `split` tiles is one item {b, first tile, end tile, ~0u}; a longer one gets ceil(n / split) items of at most `split` tiles, their fourth
+ * word consecutive scratch slots, and one fold entry {b, first slot, parts}.  items (4 words each) and folds (3 words each) may be NULL
+ * (the counts alone: call twice); *n_items, *split_blocks, *slots (each may be NULL) receive the counts. */
+int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
+                            int64_t *split_blocks, int64_t *slots);
+
 /* SURVEY 8(f)3 -- Y = A * X for k vectors at once (what the reference's unfinished `batched` path points at,
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
