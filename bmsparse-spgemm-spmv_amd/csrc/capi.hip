@@ -626,6 +626,37 @@ int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, 
     BMSP_API_END
 }
 
+int bmsp_sddmm(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void *d_Y, int64_t ldy, int k, double alpha, double beta, int flags,
+               int out_transposed, void *stream, bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    sddmm_check_args(k, ldx, ldy, beta, flags, out_transposed);
+    need(S, "matrix S"); need(d_X, "d_X"); need(d_Y, "d_Y"); need(out, "out");
+    load_kernels();
+    *out = sddmm_matrix(S, d_X, ldx, d_Y, ldy, k, alpha, beta, flags, out_transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_sddmm_values(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void *d_Y, int64_t ldy, int k, double alpha, double beta, int flags,
+                      bmsp_matrix_t out, void *stream)
+{
+    BMSP_API_BEGIN
+    sddmm_check_args(k, ldx, ldy, beta, flags, 0);
+    need(S, "matrix S"); need(d_X, "d_X"); need(d_Y, "d_Y"); need(out, "matrix out");
+    load_kernels();
+    sddmm_values_into(S, d_X, ldx, d_Y, ldy, k, alpha, beta, flags, out, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int out_transposed, bmsp_sddmm_info *info)
+{
+    BMSP_API_BEGIN
+    sddmm_check_args(k, ldx, ldy, 0.0, 0, out_transposed);
+    need(S, "matrix S"); need(info, "info");
+    sddmm_launch_info(S, k, ldx, ldy, out_transposed, info);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

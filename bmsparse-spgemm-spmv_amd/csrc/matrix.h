@@ -246,6 +246,14 @@ void matrix_diagonal(bmsp_matrix_s *A, void *d_diag, hipStream_t st);
 bmsp_matrix_s *matrix_from_diagonal(int num_rows, int num_cols, const void *d_diag, bmsp_dtype dtype, int transposed, hipStream_t st);
 bmsp_matrix_s *scale_matrix(bmsp_matrix_s *A, const void *d_left, const void *d_right, int flags, int out_transposed, hipStream_t st);
 void scale_values_into(bmsp_matrix_s *A, const void *d_left, const void *d_right, int flags, bmsp_matrix_s *out, hipStream_t st);
+// sddmm.hip: the sampled dense-dense product alpha * (X . Y^T) on S's pattern (+ beta * S, or * S) as a new matrix (tiles in layout
+// out_transposed) or into S itself / a matrix made from S by sddmm_matrix, scale_matrix or a layout conversion; what that call launches
+void sddmm_check_args(int k, int64_t ldx, int64_t ldy, double beta, int flags, int out_transposed);
+bmsp_matrix_s *sddmm_matrix(bmsp_matrix_s *S, const void *X, int64_t ldx, const void *Y, int64_t ldy, int k, double alpha, double beta,
+                            int flags, int out_transposed, hipStream_t st);
+void sddmm_values_into(bmsp_matrix_s *S, const void *X, int64_t ldx, const void *Y, int64_t ldy, int k, double alpha, double beta, int flags,
+                       bmsp_matrix_s *out, hipStream_t st);
+void sddmm_launch_info(bmsp_matrix_s *S, int k, int64_t ldx, int64_t ldy, int out_transposed, bmsp_sddmm_info *info);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -23,6 +23,7 @@ PRUNE_ABS, PRUNE_ROW_REL = 0, 1
 PRUNE_KEEP_DIAGONAL = 1
 SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
 OP_N, OP_T = 0, 1
+SDDMM_MUL_S = 1
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
@@ -36,7 +37,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -77,6 +78,13 @@ class SpmvOpInfo(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["kernel"] = self.kernel.decode()
         return d
+
+
+class SddmmInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("compulsory_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {"kernel": self.kernel.decode(), "lanes": self.lanes, "compulsory_bytes": self.compulsory_bytes}
 
 
 class ShardStats(C.Structure):
@@ -151,6 +159,9 @@ def lib():
         L.bmsp_spmv_op.argtypes = [vp, i, C.c_double, vp, C.c_double, vp, vp]
         L.bmsp_spmv_op_launch_info.argtypes = [vp, i, p(SpmvOpInfo)]
         L.bmsp_spmv_op_plan_items.argtypes = [vp, i64, i64, vp, vp, p(i64), p(i64), p(i64)]
+        L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
+        L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
+        L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
         L.bmsp_spmm_launch_info.argtypes = [vp, i, i64, i64, C.c_char_p, C.c_size_t]
         L.bmsp_spgemm.argtypes = [vp, vp, p(vp), i, i, i, vp, p(SpgemmStats)]
         L.bmsp_spgemm_symbolic.argtypes = [vp, vp, p(vp), i, i, vp, p(SpgemmStats)]
@@ -434,6 +445,14 @@ class BmSpMatrix:
         """alpha * this^T * v + beta * u without a transposed copy: pybmsp.spmv_op(op="T")"""
         return spmv_op(self, v, "T", alpha, beta, u, stream)
 
+    def sddmm(self, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, transposed=None, ldx=None, ldy=None, stream=None):
+        """alpha * (X . Y^T) on this matrix's pattern (+ beta * this, or * this) as a new matrix: pybmsp.sddmm"""
+        return sddmm(self, X, Y, k, alpha, beta, mul_s, transposed, ldx, ldy, stream)
+
+    def sddmm_(self, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, ldx=None, ldy=None, stream=None):
+        """the same into this matrix's own values (bmsp_sddmm_values with out == S)"""
+        return sddmm_values(self, self, X, Y, k, alpha, beta, mul_s, ldx, ldy, stream)
+
     def copy_values_from(self, src, stream=None):
         """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
         check(lib().bmsp_matrix_copy_values(src.h, self.h, stream))
@@ -684,6 +703,51 @@ def spmm_launch_info(A, k, ldx=None, ldy=None):
     name = C.create_string_buffer(160)
     check(lib().bmsp_spmm_launch_info(A.h, int(k), int(k if ldx is None else ldx), int(k if ldy is None else ldy), name, 160))
     return name.value.decode()
+
+
+def _sddmm_args(S, X, Y, k, ldx, ldy, mul_s):
+    i = S.info()
+    k = int(k)
+    ldx = k if ldx is None else int(ldx)
+    ldy = k if ldy is None else int(ldy)
+    if k < 1 or ldx < k or ldy < k:
+        raise ValueError("k must be >= 1 and ldx, ldy >= k (got k = %d, ldx = %d, ldy = %d)" % (k, ldx, ldy))
+    dt = np.dtype(NP_DTYPE[i["dtype"]])
+    for name, v, rows, ld in (("X", X, i["num_rows"], ldx), ("Y", Y, i["num_cols"], ldy)):
+        need = (rows - 1) * ld + k if rows else 0  # (the last row needs no padding)
+        if v is None or v.dtype != dt or v.n < need:
+            raise ValueError("%s must hold %d rows of %d entries of %s at leading dimension %d" % (name, rows, k, dt.name, ld))
+    return i, k, ldx, ldy, SDDMM_MUL_S if mul_s else 0
+
+
+def sddmm(S, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, transposed=None, ldx=None, ldy=None, stream=None):
+    """The sampled dense-dense product on S's pattern as a new matrix (bmsp_sddmm): for every stored (i, j),
+    alpha * dot(X[i, :k], Y[j, :k]) + beta * s_ij, or alpha * dot * s_ij with mul_s (beta must then be 0).  X / Y: DeviceArrays of S's
+    dtype holding num_rows / num_cols rows, row-major at leading dimension ldx / ldy (default k).  The output has S's structure in layout
+    `transposed` (None: S's layout).  Asynchronous on `stream`."""
+    i, k, ldx, ldy, flags = _sddmm_args(S, X, Y, k, ldx, ldy, mul_s)
+    lay = i["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    check(lib().bmsp_sddmm(S.h, X.ptr, ldx, Y.ptr, ldy, k, float(alpha), float(beta), flags, lay, stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def sddmm_values(out, S, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, ldx=None, ldy=None, stream=None):
+    """the values of sddmm(S, X, Y, k, ...) into `out`: S itself (in place) or a matrix made from S by sddmm() / scale() / with_layout()
+    (bmsp_sddmm_values)."""
+    _, k, ldx, ldy, flags = _sddmm_args(S, X, Y, k, ldx, ldy, mul_s)
+    check(lib().bmsp_sddmm_values(S.h, X.ptr, ldx, Y.ptr, ldy, k, float(alpha), float(beta), flags, out.h, stream))
+    return out
+
+
+def sddmm_launch_info(S, k, ldx=None, ldy=None, transposed=None):
+    """{"kernel", "lanes", "compulsory_bytes"} of the launch sddmm(S, X, Y, k, ldx=ldx, ldy=ldy) makes with 16-byte aligned X and Y
+    (bmsp_sddmm_launch_info)."""
+    k = int(k)
+    lay = S.info()["transposed"] if transposed is None else int(bool(transposed))
+    info = SddmmInfo()
+    check(lib().bmsp_sddmm_launch_info(S.h, k, k if ldx is None else int(ldx), k if ldy is None else int(ldy), lay, C.byref(info)))
+    return info.as_dict()
 
 
 # bmSparse_mult(A, B, C, mode, VERBOSE, tc_version)

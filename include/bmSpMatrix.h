@@ -388,6 +388,26 @@ inline void bmSparse_scale(bmSpMatrix<valueType> &A, const typename bmsp::vector
 {
     C = A.scale(left, right, flags, transposed_layout);
 }
+/* SDDMM (bmsp_sddmm / bmsp_sddmm_values): C = alpha * (X . Y^T) on S's pattern + beta * S, or alpha * (X . Y^T) * S under flags =
+ * BMSP_SDDMM_MUL_S (beta must then be 0).  X (num_rows x k) and Y (num_cols x k) are row-major device pointers of S's value type at
+ * leading dimensions ldx / ldy (<= 0: k).  C receives S's structure in the layout asked for; the _values form writes into S itself (C is
+ * S) or into a C made from S by bmSparse_sddmm, bmSparse_scale or with_layout.  Synchronous like bmSparse_scale. */
+template <class valueType>
+inline void bmSparse_sddmm(bmSpMatrix<valueType> &S, const valueType *X, const valueType *Y, int k, bmSpMatrix<valueType> &C, double alpha = 1.0,
+                           double beta = 0.0, int flags = 0, bool transposed_layout = false, int64_t ldx = 0, int64_t ldy = 0)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_sddmm(S.handle(), X, ldx > 0 ? ldx : k, Y, ldy > 0 ? ldy : k, k, alpha, beta, flags, transposed_layout ? 1 : 0, nullptr, &c));
+    bmsp::check(bmsp_synchronize());
+    C.reset(c);
+}
+template <class valueType>
+inline void bmSparse_sddmm_values(bmSpMatrix<valueType> &S, const valueType *X, const valueType *Y, int k, bmSpMatrix<valueType> &C,
+                                  double alpha = 1.0, double beta = 0.0, int flags = 0, int64_t ldx = 0, int64_t ldy = 0)
+{
+    bmsp::check(bmsp_sddmm_values(S.handle(), X, ldx > 0 ? ldx : k, Y, ldy > 0 ? ldy : k, k, alpha, beta, flags, C.handle(), nullptr));
+    bmsp::check(bmsp_synchronize());
+}
 
 /* The same product sharded over one process per GPU (bmsp_spgemm_sharded): every rank passes the same A and B, multiplies
  * its block-row panel of A and returns the whole C. */

@@ -337,6 +337,53 @@ int bmsp_spmv_op_launch_info(bmsp_matrix_t A, int op, bmsp_spmv_op_info *info);
 int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
                             int64_t *split_blocks, int64_t *slots);
 
+/* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
+ *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
+ * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
+ * residual of a sparse factorisation on its pattern).  Nothing in the reference is replaced: it has no such entry point.
+ *   Operands: X is num_rows x k, row-major, leading dimension ldx >= k; Y is num_cols x k, row-major, leading dimension ldy >= k; elements
+ *       of S's dtype (fp16 for F16), bmsp_spmm's convention for its X.  Matrix coordinates, whatever S's tile layout.  The padding columns
+ *       k <= t < ld are never read into a result, rows at or beyond num_rows / num_cols are never read (the ragged last block-row and
+ *       block-column).
+ *   Dot product: products and sums in fp32 (double for F64); F16 operands are widened exactly, so their products are exact in fp32.  The
+ *       order of summation is the implementation's and contraction into fused multiply-adds is allowed, but d is a pure function of the
+ *       inputs and the two switches below: no atomic, no dependence on scheduling, two calls with the same inputs give the same bits.
+ *   Epilogue: alpha and beta are rounded once to the arithmetic type (fp32; double for F64); each operation is rounded on its own, never
+ *       contracted (as bmsp_matrix_add).  Default form c = fl(fl(alpha * d) + fl(beta * s)); with beta == 0 after that rounding s is not
+ *       read: c = fl(alpha * d), a NaN stored in S does not propagate.  BMSP_SDDMM_MUL_S: c = fl(fl(alpha * d) * s); beta must be 0.  F16
+ *       outputs are rounded once more to fp16, round-to-nearest-even (the result may overflow to +-Inf).  Subnormals are kept.
+ *   bmsp_sddmm: `out` is a fresh pool-owned matrix of S's shape and dtype with tiles in layout out_transposed (S may have either); its
+ *       keys, bitmaps, offsets and block-row pointer equal bmsp_matrix_convert_layout(S, out_transposed)'s bit for bit: every coordinate is
+ *       kept, results equal to 0 included.  The output remembers S as a bmsp_matrix_scale output does, so bmsp_sddmm_values,
+ *       bmsp_matrix_scale_values and bmsp_matrix_copy_values accept it later.  S and its caches are not modified.  Asynchronous on
+ *       `stream`: nothing is read back, the call does not synchronise.
+ *   bmsp_sddmm_values: the same value pass into an existing matrix.  out == S works in place.  Any other `out` must have been made from S
+ *       by bmsp_sddmm, bmsp_matrix_scale or bmsp_matrix_convert_layout while S's STRUCTURE has not changed since (the uid rule of
+ *       bmsp_matrix_scale_values); anything else -- an unrelated handle, a bmsp_matrix_transpose output -- is BMSP_ERR_INVALID.  Drops
+ *       out's value-derived caches as bmsp_matrix_scale_values does (an in-place S's included; dropping existing ones synchronises the
+ *       device).  S is never modified unless it is `out`.
+ *   Kernels: sddmm_value_kernel (vector ALU, 1 or 8 lanes per tile, every dtype) and sddmm_tile_kernel (matrix cores, F16 and F32: a
+ *       tile's 64 candidates as one 8 x k by k x 8 product, two tiles per MFMA).  The tile kernel needs X, Y, ldx and ldy 16-byte aligned;
+ *       see README for when it is the default.  Switches, read per call: BMSP_SDDMM_KERNEL=value|tile forces a side (a forced `tile` on
+ *       F64 or misaligned operands runs the value kernel), BMSP_SDDMM_LANES=1/8 the lanes per tile of the value kernel.
+ *   bmsp_sddmm_launch_info: the launcher's own decision for (S, k, ldx, ldy) with 16-byte aligned X and Y, made by the function the
+ *       launcher itself calls: the kernel by name ("sddmm_value_kernel<1>" / "<8>", "sddmm_tile_kernel", "none (empty matrix)"), the lanes
+ *       per tile of the value kernel (0 for the tile kernel) and the bytes the launch must move.  Counting rule: 24 B of structure per
+ *       tile (key, bitmap, offset); S's values as read (the info call has no beta: a beta == 0 launch moves nnz elements fewer); the
+ *       values written; k elements for every X row and every Y row a tile touches, counted once per tile that touches it -- the tile
+ *       kernel touches the min(8, rows left) X rows and min(8, columns left) Y rows of each tile, the value kernel the rows and columns
+ *       of the tile that hold a stored value.  Reads S's keys and bitmaps back (it synchronises).  Reporting only.
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles: k < 1; ldx < k or ldy < k; flags with unknown
+ *   bits; BMSP_SDDMM_MUL_S with beta != 0; out_transposed not 0 / 1; null S, d_X, d_Y, out, info; row-panel views.  BMSP_ERR_LIMIT: 2^32
+ *   tiles or values or more. */
+#define BMSP_SDDMM_MUL_S 1   /* flags bit 0: c = fl(fl(alpha*d) * s) instead of fl(fl(alpha*d) + fl(beta*s)) */
+int bmsp_sddmm(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void *d_Y, int64_t ldy, int k,
+               double alpha, double beta, int flags, int out_transposed, void *stream, bmsp_matrix_t *out);
+int bmsp_sddmm_values(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void *d_Y, int64_t ldy, int k,
+                      double alpha, double beta, int flags, bmsp_matrix_t out, void *stream);
+typedef struct { char kernel[64]; int lanes; int64_t compulsory_bytes; } bmsp_sddmm_info;
+int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int out_transposed, bmsp_sddmm_info *info);
+
 /* SURVEY 8(f)3 -- Y = A * X for k vectors at once (what the reference's unfinished `batched` path points at,
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
