@@ -178,13 +178,14 @@ int mac_f32_exp_floor(hipStream_t st);
 bool launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
                          bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
 bool mac_strip_eligible(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, uint64_t candidates, uint64_t n_tasks, hipStream_t st);
-bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st);
+// ignore_values: the answer as if both operands held ordinary finite values -- the structural half of the predicate alone
+bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st, bool ignore_values = false);
 bool mac_strip_fits_c(bmsp_matrix_s *C, hipStream_t st);
 uint32_t mac_strip_row_cap();
 int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st);  // returns the BMSP_MAC_* variant that ran (strip, or row-sparse for V15 numerics on nearly empty tiles)
-bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);  // a numeric stage that works from C's structure alone exists for these operands
+bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values = false);  // a numeric stage that works from C's structure alone exists for these operands
 void ensure_csr32(bmsp_matrix_s *m, hipStream_t st);
-bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);
+bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values = false);
 void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
 bool mac_rowsparse_fits_c(bmsp_matrix_s *C, hipStream_t st);  // every block-row of C within the row-sparse kernel's table (768 tiles)
 bool rowmerge_symbolic(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const uint64_t *first_pos, uint64_t total, uint32_t row_cap,

@@ -1144,7 +1144,16 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         run_t2();
         const bool rm_on = !rm_off && total && (mode == BMSP_SORT_AUTO || rm_force);
         bool try_strip = rm_on && strip_allowed && !strip_tried && hint != 2 && hint != 3 && hint != 4;
-        if (try_strip) try_strip = mac_structure_numeric_ok(A, B, tc_version, st);
+        // strip mode left out ONLY because of what the operands hold (the cached value figures: non-finite values, fp32 exponents outside
+        // the matrix pipe's range -- the structural half of the predicate accepts the pair): the mode that runs instead says nothing about
+        // what the pair's structure needs, and values change (bmsp_matrix_invalidate(m, 0), copy / add / scale / sddmm into a handle) --
+        // it is not remembered, or the pair would stay off strip mode for good.  A structural refusal (hub block-rows, tile fill, views)
+        // is remembered as before: only the first product of such a pair pays for a pass that does not fit.
+        bool strip_refused_by_values = false;
+        if (try_strip) {
+            try_strip = mac_structure_numeric_ok(A, B, tc_version, st);
+            strip_refused_by_values = !try_strip && mac_structure_numeric_ok(A, B, tc_version, st, true);
+        }
         if (try_strip) {
             uint64_t surv = 0, cand = 0;
             if (rowmerge_symbolic(A, B, C.get(), first_pos.p, total, mac_strip_row_cap(), &surv, &cand, st)) {
@@ -1161,10 +1170,11 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
             // task-list mode (a wave per block-row, hash table of ~900 C tiles); operands with hub block-rows: column windows (a workgroup
             // per block-row and window of block columns, dense tables: rowwindow.hip); neither applies: the pipeline
             int got = 0;
+            const bool tasklist_tried = hint != 4 && !win_force;
             if (hint != 4 && !win_force && rowmerge_tasklist(A, B, C.get(), first_pos.p, total, rm_tasks, task_begin, c_of_wave, &n_tasks, st)) got = 2;
             else if (!win_off && rowmerge_windowed(A, B, C.get(), first_pos.p, total, rm_tasks, task_begin, c_of_wave, &n_tasks, st)) got = 4;
             if (got) {
-                remember(got);
+                if (!strip_refused_by_values) remember(got);
                 have_tasks = true;
                 tasks_sorted = rm_tasks.p;
                 c_size = (uint32_t)C->block_num;
@@ -1173,6 +1183,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
                 S->bmp_reduction = (int64_t)(total - n_tasks);
                 S->sort_path = got == 2 ? BMSP_SORT_PATH_ROWMERGE : BMSP_SORT_PATH_ROWWINDOW;
                 if (got == 2) S->sort_long = BMSP_ROWMERGE_TASKLIST;
+                else S->sort_long = tasklist_tried ? BMSP_ROWWINDOW_AFTER_TASKLIST : 0;
                 finish_structure();
                 tm.mark(9);
             } else {
