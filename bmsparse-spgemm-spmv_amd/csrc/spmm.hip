@@ -394,7 +394,8 @@ void launch_vstream(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64
     const uint32_t chunks = (uint32_t)((k + KK - 1) / KK);
     DevBuf<Ac> carry(A->spmv_plan_long ? (size_t)n_items * chunks * 8 * KK : 1);
     DevBuf<uint32_t> counters((size_t)(A->spmv_plan_long ? A->spmv_plan_long : 1) * chunks);
-    BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
+    // without long block-rows no kernel touches the two buffers and the call does not synchronise: nothing may be enqueued on them either
+    if (A->spmv_plan_long) BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
     const int x_vec = sizeof(T) == 4 && ((uintptr_t)X & 15u) == 0 && ldx % 4 == 0 && k % KK == 0;
     hipLaunchKernelGGL((spmm_vstream_kernel<T, KK>), dim3(n_items, chunks), dim3(64), 0, st, plan_items(A), A->keys, A->offsets, (const T *)A->values,
                        A->spmv_pos, (uint32_t)A->spmv_pos_base, (uint32_t)A->spmv_pos_count, (uint32_t)((size_t)A->values_extent() * sizeof(T)),
@@ -412,7 +413,7 @@ void launch_wide(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t 
     const uint32_t chunks = (uint32_t)((k + 63) / 64);
     DevBuf<Ac> carry(A->spmv_plan_long ? (size_t)n_items * chunks * 8 * 64 : 1);
     DevBuf<uint32_t> counters((size_t)(A->spmv_plan_long ? A->spmv_plan_long : 1) * chunks);
-    BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
+    if (A->spmv_plan_long) BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
     hipLaunchKernelGGL((spmm_wide_kernel<T>), dim3((n_items + 3) / 4, chunks), dim3(kThreads), 0, st, plan_items(A), n_items, A->keys, A->bmps, A->offsets,
                        (const T *)A->values, (const T *)X, (Ac *)Y, carry.p, counters.p, (uint32_t)A->num_rows, (uint32_t)A->num_cols, (uint32_t)k,
                        (uint64_t)ldx, (uint64_t)ldy);
@@ -429,7 +430,7 @@ void launch_kk(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ld
     // the plan's own carry / counters serve the single-vector sweep; a k-wide product needs k-wide slots
     DevBuf<Ac> carry(A->spmv_plan_long ? (size_t)n_items * chunks * 8 * KK : 1);
     DevBuf<uint32_t> counters((size_t)(A->spmv_plan_long ? A->spmv_plan_long : 1) * chunks);
-    BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
+    if (A->spmv_plan_long) BMSP_HIP(hipMemsetAsync(counters.p, 0, 4 * counters.n, st));
     hipLaunchKernelGGL((spmm_kernel<T, KK>), dim3((n_items + 3) / 4, chunks), dim3(kThreads), 0, st, plan_items(A), n_items, A->rowptr, A->keys, A->bmps,
                        A->offsets, (const T *)A->values, (const T *)X, (Ac *)Y, carry.p, counters.p, (uint32_t)A->num_rows, (uint32_t)A->num_cols,
                        (uint32_t)k, (uint64_t)ldx, (uint64_t)ldy);

@@ -85,7 +85,8 @@ int bmsp_matrix_from_coo(int num_rows, int num_cols, int64_t nnz, const int *row
 /* Same builder from COO triples already resident on the device (rows/cols int32, vals float64).  The contract is that of
  * bmsp_matrix_from_coo: every index lies in [0, num_rows) x [0, num_cols) and dtype is one of the three bmsp_dtype values.
  * The builder's own kernels check it on the device (no extra launch or synchronisation); a violation returns
- * BMSP_ERR_INVALID, leaves *out untouched and nothing allocated. */
+ * BMSP_ERR_INVALID, leaves *out untouched and nothing allocated.  Runs on `stream` and synchronises it before it returns (the tile
+ * count is read back, the temporaries go back to the pool). */
 int bmsp_matrix_from_coo_device(int num_rows, int num_cols, int64_t nnz, const int *d_rows, const int *d_cols,
                                 const double *d_vals, int transposed, bmsp_dtype dtype, void *stream,
                                 bmsp_matrix_t *out);
@@ -237,7 +238,8 @@ int bmsp_matrix_block_row_ptr(bmsp_matrix_t m, const uint32_t **d_rowptr, int64_
  * entry per stored value (2 * nnz bytes of device memory; BMSP_SPMV_NO_POSCACHE=1 or a size above BMSP_SPMV_POSCACHE_MAX bytes,
  * default 4 GiB, keeps the bitmap decode inside the kernel instead); bit 1 = the packed operand records of the SpGEMM block-MAC (both
  * operand roles, incl. the dense fp16 tile copies of the MFMA kernels: 128 bytes per block).
- * Idempotent; asynchronous on `stream` except for the scalar read-backs of the plan. */
+ * Idempotent.  Runs on `stream` and synchronises it whenever it builds something (the scalar read-backs of the plan, the finite /
+ * exponent flags of the operand records, temporaries that go back to the pool); a call that finds everything built returns at once. */
 #define BMSP_PREPARE_SPMV 1
 #define BMSP_PREPARE_SPGEMM 2
 int bmsp_matrix_prepare(bmsp_matrix_t m, int what, void *stream);
@@ -247,13 +249,15 @@ int bmsp_matrix_prepare(bmsp_matrix_t m, int what, void *stream);
 int bmsp_matrix_to_coo_host(bmsp_matrix_t m, int *rows, int *cols, double *vals);
 
 /* SURVEY 8(f)2 -- the same expansion with the result left on the device, as COO or CSR sorted by (row, col), so a product can
- * feed CSR consumers without a host round trip.  d_rows/d_cols/d_vals hold nnz entries, d_row_offsets num_rows+1. */
+ * feed CSR consumers without a host round trip.  d_rows/d_cols/d_vals hold nnz entries, d_row_offsets num_rows+1.  Both run on
+ * `stream` and synchronise it before they return (their temporaries go back to the pool). */
 int bmsp_matrix_to_coo_device(bmsp_matrix_t m, int *d_rows, int *d_cols, double *d_vals, void *stream);
 int bmsp_matrix_to_csr_device(bmsp_matrix_t m, int *d_row_offsets, int *d_cols, double *d_vals, void *stream);
 /* ... and the builder from a device-resident CSR (int32 offsets/columns, float64 values; duplicates summed as in from_coo).
  * Contract, checked on the device like bmsp_matrix_from_coo_device's (for nnz == 0 at the price of one small launch and a
  * synchronise, which an empty matrix did not have): d_row_offsets[0] == 0, d_row_offsets[num_rows] == nnz, no
- * offset larger than the next, every column in [0, num_cols), a known dtype; otherwise BMSP_ERR_INVALID and no matrix. */
+ * offset larger than the next, every column in [0, num_cols), a known dtype; otherwise BMSP_ERR_INVALID and no matrix.  Runs on
+ * `stream` and synchronises it before it returns, as bmsp_matrix_from_coo_device. */
 int bmsp_matrix_from_csr_device(int num_rows, int num_cols, int64_t nnz, const int *d_row_offsets, const int *d_cols,
                                 const double *d_vals, int transposed, bmsp_dtype dtype, void *stream, bmsp_matrix_t *out);
 
@@ -262,7 +266,8 @@ int bmsp_matrix_from_csr_device(int num_rows, int num_cols, int64_t nnz, const i
  * that the comparand lacks (the reference would walk out of bounds). */
 int bmsp_matrix_compare(bmsp_matrix_t m, int64_t nnz, const int *rows, const int *cols, const double *vals,
                         double *mean_rel_err, int64_t *missing);
-/* the same comparison with a device-resident comparand, entirely on the device (large products) */
+/* the same comparison with a device-resident comparand, entirely on the device (large products); runs on `stream` and
+ * synchronises it before it returns (the two results are host values) */
 int bmsp_matrix_compare_device(bmsp_matrix_t m, int64_t nnz, const int *d_rows, const int *d_cols, const double *d_vals,
                                double *mean_rel_err, int64_t *missing, void *stream);
 
@@ -276,7 +281,9 @@ int bmsp_matrix_compare_device(bmsp_matrix_t m, int64_t nnz, const int *d_rows, 
 
 /* bmSparse_SpMV<VI,VO>(A, v, u, batched)  -- src/bmSparse_SPMV.cu:191-230.   u = A * v
  * v: device, num_cols entries of A's dtype; u: device, num_rows entries (float for F32/F16, double for F64).
- * Asynchronous on `stream`; A is not modified.  Rows of empty block-rows are written as 0.
+ * Asynchronous on `stream` once the cached sweep plan of A exists; the call that builds the plan, the position cache or the chunk
+ * cache (the first sweep of a handle that takes a kernel which needs them, or bmsp_matrix_prepare) synchronises `stream` for their
+ * scalar read-backs.  A is not modified.  Rows of empty block-rows are written as 0.
  * One stream per handle at a time: the cached sweep plan holds the hub rows' carry slots and arrival counters, so two sweeps of the
  * SAME handle must not be in flight on different streams (different handles may). */
 int bmsp_spmv(bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *stream);
@@ -389,7 +396,11 @@ int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
  * Every Y[i][j], i < num_rows, j < k, is written (0 for a row without stored values); the padding columns j >= k of a strided Y
  * and of X are neither written nor read into the result.  On a row-panel view (bmsp_matrix_row_panel) the view keeps the parent's
- * num_rows, so the rows outside the panel are rows without stored values: they are written as exact 0, not left untouched. */
+ * num_rows, so the rows outside the panel are rows without stored values: they are written as exact 0, not left untouched.
+ * Runs on `stream`; the first product of a handle builds bmsp_spmv's plan and synchronises as that call does.  After that the call is
+ * asynchronous on `stream` unless A has block-rows long enough to be split over several work items: their k-wide carry slots and
+ * arrival counters are temporaries, and the call synchronises `stream` before they go back to the pool.  Without such block-rows
+ * nothing is enqueued on a temporary.  One stream per handle at a time, as for bmsp_spmv. */
 int bmsp_spmm(bmsp_matrix_t A, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, int k, void *stream);
 
 /* The kernel bmsp_spmm(A, X, ldx, Y, ldy, k) launches, by name: "spmm_vstream_kernel<4>" / "<8>", "spmm_kernel<4>" / "<16>" / "<64>",
@@ -449,7 +460,9 @@ typedef struct {
  * switch (:1132-1155): 5 = vector-ALU kernel with the reference's V15 numerics (each product rounded to the
  * input type, fp32 accumulate); 1..4 = matrix-core (MFMA) kernel: exact products, fp32 accumulate.
  * verbose != 0 prints the reference's stage lines to stdout.  stats may be NULL.
- * Synchronous with respect to the host on return (the reference ends with cudaDeviceSynchronize, :1158).
+ * Runs on `stream`; synchronous with respect to the host on return (the reference ends with cudaDeviceSynchronize, :1158): `stream`
+ * is synchronised, every temporary is back in the pool.  The same holds for bmsp_spgemm_symbolic, bmsp_spgemm_numeric and the sharded
+ * products below.
  * A product with 2^32 or more candidate block pairs (more than one task list can index) is run block-row panel after panel
  * and concatenated; stats then hold the sums over the panels (stage lines are printed per panel). */
 int bmsp_spgemm(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t *C, int mode, int tc_version, int verbose,
@@ -501,7 +514,8 @@ int bmsp_selftest_tile_product(int *mismatches);
 /* bb_segsort<K,T>(keys, vals, n, segs, length)  -- include/bb_segsort-master/bb_segsort.h:35-192,
  * instantiated by the reference with K = uint64_t, T = 16-byte task_list_elem (src/bmSparse_SPGEMM.cu:1010).
  * Sorts every segment [segs[i], segs[i+1]) (last ends at n) ascending by key, in place, STABLY
- * (bb_segsort is unstable).  d_vals may be NULL (keys only). val_bytes in {4, 8, 16}. */
+ * (bb_segsort is unstable).  d_vals may be NULL (keys only). val_bytes in {4, 8, 16}.  Runs on `stream` and synchronises it before
+ * it returns (work lists and the second key / value arrays are temporaries). */
 int bmsp_segsort_u64(uint64_t *d_keys, void *d_vals, int val_bytes, int64_t n, const int *d_segs,
                      int64_t num_segs, void *stream);
 
@@ -575,7 +589,8 @@ int bmsp_spgemm_sharded(bmsp_comm_t c, bmsp_matrix_t A, bmsp_matrix_t B, bmsp_ma
 int bmsp_spgemm_sharded_ex(bmsp_comm_t c, bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t *C, int mode, int tc_version, int verbose,
                            void *stream, bmsp_spgemm_stats *stats, bmsp_shard_stats *shard, int gather, int rounds);
 /* u = A * v with A cut into block-row panels balanced by stored values, v replicated; every rank sweeps its panel (writing only its
- * own rows of u), the row slices are exchanged in place and all ranks return the whole u (num_rows entries).  The panel view and its sweep plan are cached on A across calls. */
+ * own rows of u), the row slices are exchanged in place and all ranks return the whole u (num_rows entries).  The panel view and its sweep plan are cached on A across calls.
+ * Runs on `stream` and synchronises it before it returns (the exchange; the loopback communicator's scratch vectors). */
 int bmsp_spmv_sharded(bmsp_comm_t c, bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *stream, bmsp_shard_stats *shard);
 
 /* ---- host CSR (class CSRMatrix, include/CSRMatrix.h:13-21; declared only in the reference; backed by

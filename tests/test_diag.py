@@ -6,7 +6,8 @@ import ctypes as C
 import os
 import numpy as np
 import pytest
-from test_transpose import entries, assert_same_arrays, snapshot, assert_unchanged, _hip, _write_values
+from stream_gate import _hip
+from test_transpose import entries, assert_same_arrays, snapshot, assert_unchanged, _write_values
 from test_add import stored, check_structure, assert_same_values
 
 pytestmark = pytest.mark.gpu

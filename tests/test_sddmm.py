@@ -25,7 +25,8 @@ import os
 import subprocess
 import numpy as np
 import pytest
-from test_transpose import snapshot, assert_unchanged, assert_same_arrays, entries, _hip
+from stream_gate import _hip
+from test_transpose import snapshot, assert_unchanged, assert_same_arrays, entries
 
 pytestmark = pytest.mark.gpu
 

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import util
+from util import SPMV_LAUNCHES
 
 NPDT = {0: np.float32, 1: np.float16, 2: np.float64}
 INF, NAN = float("inf"), float("nan")
@@ -784,22 +785,6 @@ def _poisoned_x(n, empty_blocks, width=None):
         x[lo:hi:2] = INF
         x[lo + 1:hi:2] = NAN
     return x, x0
-
-
-SPMV_LAUNCHES = {
-    # name -> (matrix kind, environment, variant, kernel name prefix)
-    "vstream_cached_atomic": ("sparse", {"BMSP_SPMV_NOCHUNK": "1", "BMSP_SPMV_RED": "0"}, 0, "spmv_vstream_kernel<kCached, kAtomic>"),
-    "vstream_cached_sorted": ("sparse", {"BMSP_SPMV_NOCHUNK": "1", "BMSP_SPMV_RED": "1"}, 0, "spmv_vstream_kernel<kCached, kSorted>"),
-    "vstream_decode_atomic": ("sparse", {"BMSP_SPMV_NO_POSCACHE": "1", "BMSP_SPMV_RED": "0"}, 0, "spmv_vstream_kernel<kDecode, kAtomic>"),
-    "vstream_decode_sorted": ("sparse", {"BMSP_SPMV_NO_POSCACHE": "1", "BMSP_SPMV_RED": "1"}, 0, "spmv_vstream_kernel<kDecode, kSorted>"),
-    "rowgroup": ("dense", {}, 3, "spmv_rowgroup_kernel"),
-    "rowgroup_sparse": ("sparse", {}, 3, "spmv_rowgroup_kernel"),
-    "blockrow_batched": ("dense", {}, 1, "spmv_blockrow_kernel<64"),
-    "blockrow_batched_sparse": ("sparse", {}, 1, "spmv_blockrow_kernel<64"),
-    "blockrow_8": ("sparse", {}, 2, "spmv_blockrow_kernel<8"),
-    "sweep_round1": ("sparse", {"BMSP_SPMV_OLD": "1"}, 0, "spmv_sweep_kernel"),
-    "sweep_round1_full": ("dense", {"BMSP_SPMV_NO_ROWGROUP": "1"}, 0, "spmv_sweep_kernel<FULL>"),
-}
 
 
 @pytest.mark.gpu

@@ -10,7 +10,8 @@ import os
 import subprocess
 import numpy as np
 import pytest
-from test_transpose import snapshot, assert_unchanged, _hip, _write_values
+from stream_gate import _hip
+from test_transpose import snapshot, assert_unchanged, _write_values
 from test_add import stored
 
 pytestmark = pytest.mark.gpu

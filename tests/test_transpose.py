@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 import util
+from stream_gate import _hip
 
 pytestmark = pytest.mark.gpu
 
@@ -335,21 +336,6 @@ def test_row_panel_views_are_refused(bmsp):
         with pytest.raises(bmsp.BmspError) as e:
             op()
         assert e.value.status == -1 and "view" in str(e.value)
-
-
-def _hip():
-    """the HIP runtime libbmsp.so runs on (the same loaded file, so one runtime in the process)."""
-    bmsp_lib_path = None
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            bmsp_lib_path = line.split()[-1]
-            break
-    assert bmsp_lib_path, "libamdhip64 is not loaded"
-    H = C.CDLL(bmsp_lib_path)
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
 
 
 def test_non_default_stream(bmsp):

@@ -50,3 +50,20 @@ def assert_bmsp_equal_exact(oracle_m, keys, bmps, offsets, values, np_dtype):
     got = np.asarray(values)
     assert got.shape == ref.shape
     np.testing.assert_array_equal(got.view(np.uint8), ref.view(np.uint8))
+
+
+# every kernel bmsp_spmv can be made to launch on the gap matrices of test_spgemm_special_values._gap_matrix
+SPMV_LAUNCHES = {
+    # name -> (matrix kind, environment, variant, kernel name prefix)
+    "vstream_cached_atomic": ("sparse", {"BMSP_SPMV_NOCHUNK": "1", "BMSP_SPMV_RED": "0"}, 0, "spmv_vstream_kernel<kCached, kAtomic>"),
+    "vstream_cached_sorted": ("sparse", {"BMSP_SPMV_NOCHUNK": "1", "BMSP_SPMV_RED": "1"}, 0, "spmv_vstream_kernel<kCached, kSorted>"),
+    "vstream_decode_atomic": ("sparse", {"BMSP_SPMV_NO_POSCACHE": "1", "BMSP_SPMV_RED": "0"}, 0, "spmv_vstream_kernel<kDecode, kAtomic>"),
+    "vstream_decode_sorted": ("sparse", {"BMSP_SPMV_NO_POSCACHE": "1", "BMSP_SPMV_RED": "1"}, 0, "spmv_vstream_kernel<kDecode, kSorted>"),
+    "rowgroup": ("dense", {}, 3, "spmv_rowgroup_kernel"),
+    "rowgroup_sparse": ("sparse", {}, 3, "spmv_rowgroup_kernel"),
+    "blockrow_batched": ("dense", {}, 1, "spmv_blockrow_kernel<64"),
+    "blockrow_batched_sparse": ("sparse", {}, 1, "spmv_blockrow_kernel<64"),
+    "blockrow_8": ("sparse", {}, 2, "spmv_blockrow_kernel<8"),
+    "sweep_round1": ("sparse", {"BMSP_SPMV_OLD": "1"}, 0, "spmv_sweep_kernel"),
+    "sweep_round1_full": ("dense", {"BMSP_SPMV_NO_ROWGROUP": "1"}, 0, "spmv_sweep_kernel<FULL>"),
+}
