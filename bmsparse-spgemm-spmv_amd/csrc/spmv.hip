@@ -973,8 +973,10 @@ __global__ __launch_bounds__(kThreads) void spmv_blockrow_kernel(const uint32_t 
 // tiles; lane j of the group takes tile positions 4j .. 4j+3 (half a tile row): ONE 16-byte load of the <= 4 consecutive stored
 // values behind rank(4j) -- the whole wave moves 1 KB of values per instruction when tiles are full -- against one 16-byte load
 // of the four x entries (block column cached in L1/L2: neighbouring block-rows of a banded matrix read the same x lines).
-// Partly filled nibbles are expanded with three selects; sums stay in registers for the whole block-row (no LDS, no atomics:
-// y is bit-reproducible), the two half-rows meet in one DPP add, 8 lanes store the 8 rows.
+// Partly filled nibbles are expanded with three selects, and the x entries of their unstored positions are selected to zero with four
+// more (the sum is over the STORED entries: an Inf or NaN of x beside a stored column must not meet the expansion's 0); sums stay in
+// registers for the whole block-row (no LDS, no atomics: y is bit-reproducible), the two half-rows meet in one DPP add, 8 lanes store
+// the 8 rows.
 template <typename T, int U>
 __global__ __launch_bounds__(kThreads) void spmv_rowgroup_kernel(const uint32_t *__restrict__ rowptr, const uint64_t *__restrict__ keys,
                                                                  const uint64_t *__restrict__ bmps, const uint64_t *__restrict__ offsets,
@@ -1049,20 +1051,23 @@ __global__ __launch_bounds__(kThreads) void spmv_rowgroup_kernel(const uint32_t 
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint32_t n = nib[u];
-                A e0, e1, e2, e3;
+                A e0, e1, e2, e3, x0 = xv[u][0], x1 = xv[u][1], x2 = xv[u][2], x3 = xv[u][3];
                 if (__all(n == 0xfu || n == 0u)) {  // full (or absent) nibbles everywhere: values already sit at their positions
                     e0 = av[u][0]; e1 = av[u][1]; e2 = av[u][2]; e3 = av[u][3];
-                    if (n == 0u) { e0 = e1 = e2 = e3 = A(0); }
+                    if (n == 0u) { e0 = e1 = e2 = e3 = A(0); }  // (its x was not loaded either: the out-of-range offset reads 0)
                 } else {
-                    // stored values of the nibble are consecutive: position q holds value number popc(bits before q)
+                    // stored values of the nibble are consecutive: position q holds value number popc(bits before q).  An unstored
+                    // position contributes nothing, whatever x holds there (bmsp.h: the sum is over the STORED entries): its x is
+                    // selected to zero by the same bit as its value, so an Inf or NaN of x next to a stored column never meets a 0
                     const bool b0 = n & 8u, b1 = n & 4u, b2 = n & 2u, b3 = n & 1u;
                     const uint32_t i2 = (uint32_t)b0 + (uint32_t)b1, i3 = i2 + (uint32_t)b2;
                     e0 = b0 ? av[u][0] : A(0);
                     e1 = b1 ? (b0 ? av[u][1] : av[u][0]) : A(0);
                     e2 = b2 ? (i2 == 0 ? av[u][0] : (i2 == 1 ? av[u][1] : av[u][2])) : A(0);
                     e3 = b3 ? (i3 == 0 ? av[u][0] : (i3 == 1 ? av[u][1] : (i3 == 2 ? av[u][2] : av[u][3]))) : A(0);
+                    x0 = b0 ? x0 : A(0); x1 = b1 ? x1 : A(0); x2 = b2 ? x2 : A(0); x3 = b3 ? x3 : A(0);
                 }
-                acc += e0 * xv[u][0] + e1 * xv[u][1] + e2 * xv[u][2] + e3 * xv[u][3];
+                acc += e0 * x0 + e1 * x1 + e2 * x2 + e3 * x3;
             }
             t += U;
 #pragma unroll

@@ -283,7 +283,17 @@ int bmsp_matrix_compare_device(bmsp_matrix_t m, int64_t nnz, const int *d_rows, 
  * v: device, num_cols entries of A's dtype; u: device, num_rows entries (float for F32/F16, double for F64).
  * Asynchronous on `stream` once the cached sweep plan of A exists; the call that builds the plan, the position cache or the chunk
  * cache (the first sweep of a handle that takes a kernel which needs them, or bmsp_matrix_prepare) synchronises `stream` for their
- * scalar read-backs.  A is not modified.  Rows of empty block-rows are written as 0.
+ * scalar read-backs.  A is not modified.
+ *   Sum: u_i = the sum over the STORED entries of row i of a * v -- the rule of every kernel the launcher may pick, whatever the variant:
+ *       an element of v at a column where row i stores nothing never reaches u_i, whatever it holds (Inf, NaN), inside a stored tile too
+ *       (the reference multiplies whole tiles: there 0 * Inf = NaN along a tile row).  A stored value is always
+ *       multiplied: a stored 0 against an Inf in v gives NaN, a stored Inf or NaN propagates as IEEE 754 says.  Products and sums are in
+ *       fp32 (double for F64), in the implementation's order, contraction into fused multiply-adds allowed; F16 operands are widened
+ *       exactly; subnormal operands and results are kept (no kernel flushes them, the LDS float adds of spmv_vstream_kernel<., kAtomic>
+ *       included: tests/test_spmv_special_values.py).  A row without stored entries is +0 (rows of empty block-rows too).  The sign of a
+ *       zero sum and the sign or payload of a NaN are not specified.
+ *   Pointers: d_v and d_u need the alignment of their element type and no more (a view one element into an allocation is a legal
+ *       argument); nothing before d_u[0] or behind d_u[num_rows - 1] is written.
  * One stream per handle at a time: the cached sweep plan holds the hub rows' carry slots and arrival counters, so two sweeps of the
  * SAME handle must not be in flight on different streams (different handles may). */
 int bmsp_spmv(bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *stream);
@@ -395,7 +405,9 @@ int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
  * Every Y[i][j], i < num_rows, j < k, is written (0 for a row without stored values); the padding columns j >= k of a strided Y
- * and of X are neither written nor read into the result.  On a row-panel view (bmsp_matrix_row_panel) the view keeps the parent's
+ * and of X are neither written nor read into the result.  Each column of Y is the sum bmsp_spmv defines (stored entries only, IEEE
+ * propagation of stored Inf / NaN, fp32 / double arithmetic, subnormals kept -- the LDS float adds of spmm_vstream_kernel included --,
+ * +0 for a row without stored entries), on every kernel this call may launch.  On a row-panel view (bmsp_matrix_row_panel) the view keeps the parent's
  * num_rows, so the rows outside the panel are rows without stored values: they are written as exact 0, not left untouched.
  * Runs on `stream`; the first product of a handle builds bmsp_spmv's plan and synchronises as that call does.  After that the call is
  * asynchronous on `stream` unless A has block-rows long enough to be split over several work items: their k-wide carry slots and
@@ -590,6 +602,7 @@ int bmsp_spgemm_sharded_ex(bmsp_comm_t c, bmsp_matrix_t A, bmsp_matrix_t B, bmsp
                            void *stream, bmsp_spgemm_stats *stats, bmsp_shard_stats *shard, int gather, int rounds);
 /* u = A * v with A cut into block-row panels balanced by stored values, v replicated; every rank sweeps its panel (writing only its
  * own rows of u), the row slices are exchanged in place and all ranks return the whole u (num_rows entries).  The panel view and its sweep plan are cached on A across calls.
+ * Every u_i is the sum bmsp_spmv defines (stored entries only; its special-value and subnormal rules hold panel by panel).
  * Runs on `stream` and synchronises it before it returns (the exchange; the loopback communicator's scratch vectors). */
 int bmsp_spmv_sharded(bmsp_comm_t c, bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *stream, bmsp_shard_stats *shard);
 

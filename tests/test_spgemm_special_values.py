@@ -19,14 +19,15 @@ the matrix-core kernels, which do not, must be refused by the exponent guard, an
 position, never by payload or sign: the host's default NaN and the GPU's differ in the sign bit.
 
 SpMV / SpMM (the last section): x holds Inf and NaN at every column of the block-columns in which the matrix stores NO tile, and no kernel
-may read them.  Nothing is asserted about special values of x inside a block-column that holds a tile: the oracle multiplies whole tiles
-there (0 * Inf = NaN for the positions a tile does not store) and the kernels, which multiply stored values, legitimately differ.
+may read them.  Special values of x INSIDE a block-column that holds a tile, stored Inf / NaN, subnormals and overflowing sums are the
+subject of test_spmv_special_values.py: the oracle multiplies whole tiles there (0 * Inf = NaN for the positions a tile does not store),
+the kernels multiply stored values only (bmsp.h, bmsp_spmv), so that file compares with a reference of its own.
 """
 import numpy as np
 import pytest
 
 import util
-from util import SPMV_LAUNCHES
+from util import SPMV_LAUNCHES, SPMV_CHUNK_LAYOUT, SPMM_LAUNCHES, spmv_launch_params
 
 NPDT = {0: np.float32, 1: np.float16, 2: np.float64}
 INF, NAN = float("inf"), float("nan")
@@ -788,8 +789,7 @@ def _poisoned_x(n, empty_blocks, width=None):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype", [0, 1, 2])
-@pytest.mark.parametrize("launch", list(SPMV_LAUNCHES))
+@pytest.mark.parametrize("launch,dtype", spmv_launch_params())
 def test_spmv_padding_adds_nothing(oracle, bmsp, monkeypatch, launch, dtype):
     """x = Inf / NaN wherever the matrix stores no tile (block-column 0, the last, ragged one, every seventh): the sweep must not read
     them -- no output is Inf or NaN, the result equals the sweep of x with zeros there bit for bit, and (integer inputs: exact in any
@@ -800,6 +800,8 @@ def test_spmv_padding_adds_nothing(oracle, bmsp, monkeypatch, launch, dtype):
     nr, nc, r, c, v, ebc, _ = _gap_matrix(kind)
     A = bmsp.BmSpMatrix.from_coo(nr, nc, r, c, v, dtype=dtype)
     assert bmsp.spmv_launch_info(A, variant)["kernel"].startswith(kernel), bmsp.spmv_launch_info(A, variant)
+    if launch in SPMV_CHUNK_LAYOUT:   # (the two chunk launches share the kernel's name: the layout tells them apart)
+        assert bmsp.spmv_chunk_layout(A) == SPMV_CHUNK_LAYOUT[launch]
     x, x0 = _poisoned_x(nc, ebc)
     out = []
     for xs in (x, x0):
@@ -836,19 +838,6 @@ def test_spmv_op_padding_adds_nothing(oracle, bmsp, kind, op, layout, dtype):
     if dtype == 0 and op == "N" and not layout:
         ref = oracle.bmsp_from_coo(oracle.Coo(nr, nc, r, c, v), 0, False)
         np.testing.assert_array_equal(out[0], oracle.spmv_f32(ref, x0.astype(np.float32)))
-
-
-SPMM_LAUNCHES = {
-    # name -> (matrix kind, BMSP_SPMM_NO_VSTREAM, k, kernel)
-    "vstream4": ("sparse", False, 3, "spmm_vstream_kernel<4>"),
-    "vstream8": ("sparse", False, 7, "spmm_vstream_kernel<8>"),
-    "kernel4": ("sparse", True, 3, "spmm_kernel<4>"),
-    "kernel16": ("sparse", True, 13, "spmm_kernel<16>"),
-    "wide": ("sparse", True, 21, "spmm_wide_kernel"),
-    "kernel4_dense": ("dense", False, 4, "spmm_kernel<4>"),
-    "kernel16_dense": ("dense", False, 9, "spmm_kernel<16>"),
-    "wide_dense": ("dense", False, 33, "spmm_wide_kernel"),
-}
 
 
 @pytest.mark.gpu

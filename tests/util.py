@@ -66,4 +66,29 @@ SPMV_LAUNCHES = {
     "blockrow_8": ("sparse", {}, 2, "spmv_blockrow_kernel<8"),
     "sweep_round1": ("sparse", {"BMSP_SPMV_OLD": "1"}, 0, "spmv_sweep_kernel"),
     "sweep_round1_full": ("dense", {"BMSP_SPMV_NO_ROWGROUP": "1"}, 0, "spmv_sweep_kernel<FULL>"),
+    # the chunked sweep, forced (the default takes it from a few thousand chunks only): row-sorted words and the storage-order words
+    "chunk_row_sorted": ("sparse", {"BMSP_SPMV_CHUNK": "1"}, 0, "spmv_chunk_kernel"),
+    "chunk_storage_order": ("sparse", {"BMSP_SPMV_CHUNK": "1", "BMSP_SPMV_CHUNK_SORTED": "0"}, 0, "spmv_chunk_kernel"),
+}
+# launches that exist for some dtypes only (the chunked sweep is an fp32 kernel), and what bmsp_spmv_chunk_layout must report for them
+SPMV_LAUNCH_DTYPES = {"chunk_row_sorted": (0,), "chunk_storage_order": (0,)}
+SPMV_CHUNK_LAYOUT = {"chunk_row_sorted": 2, "chunk_storage_order": 1}
+
+
+def spmv_launch_params(dtypes=(0, 1, 2)):
+    """(launch, dtype) for every entry of SPMV_LAUNCHES and every dtype its kernel exists for"""
+    return [(l, d) for l in SPMV_LAUNCHES for d in dtypes if d in SPMV_LAUNCH_DTYPES.get(l, (0, 1, 2))]
+
+
+# every SpMM kernel test_spmm.py pins, on the same two matrix kinds (spmm_kernel<64> needs 2^32 values and is out of reach)
+SPMM_LAUNCHES = {
+    # name -> (matrix kind, BMSP_SPMM_NO_VSTREAM, k, kernel)
+    "vstream4": ("sparse", False, 3, "spmm_vstream_kernel<4>"),
+    "vstream8": ("sparse", False, 7, "spmm_vstream_kernel<8>"),
+    "kernel4": ("sparse", True, 3, "spmm_kernel<4>"),
+    "kernel16": ("sparse", True, 13, "spmm_kernel<16>"),
+    "wide": ("sparse", True, 21, "spmm_wide_kernel"),
+    "kernel4_dense": ("dense", False, 4, "spmm_kernel<4>"),
+    "kernel16_dense": ("dense", False, 9, "spmm_kernel<16>"),
+    "wide_dense": ("dense", False, 33, "spmm_wide_kernel"),
 }
