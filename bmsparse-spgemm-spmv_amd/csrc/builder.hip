@@ -417,6 +417,8 @@ void drop_spmv_op_views(bmsp_matrix_s *m)
         w = bmsp_spmv_op_view();
     }
     pool_free(m->spmv_op_tmp); m->spmv_op_tmp = nullptr;
+    pool_free(m->spmm_op_scratch); m->spmm_op_scratch = nullptr; m->spmm_op_scratch_elems = 0;
+    pool_free(m->spmm_op_tmp); m->spmm_op_tmp = nullptr; m->spmm_op_tmp_elems = 0;
 }
 
 void alloc_tile_arrays(bmsp_matrix_s *m, uint64_t nb)

@@ -626,6 +626,26 @@ int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, 
     BMSP_API_END
 }
 
+int bmsp_spmm_op(bmsp_matrix_t A, int op, double alpha, const void *d_X, int64_t ldx, double beta, void *d_Y, int64_t ldy, int k, void *stream)
+{
+    BMSP_API_BEGIN
+    spmm_op_check_args(op, k, ldx, ldy);
+    need(A, "matrix A"); need(d_X, "d_X"); need(d_Y, "d_Y");
+    load_kernels();
+    spmm_op(A, op, alpha, d_X, ldx, beta, d_Y, ldy, k, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spmm_op_launch_info(bmsp_matrix_t A, int op, int k, int64_t ldx, int64_t ldy, bmsp_spmm_op_info *info)
+{
+    BMSP_API_BEGIN
+    spmm_op_check_args(op, k, ldx, ldy);
+    need(A, "matrix A"); need(info, "info");
+    load_kernels();
+    spmm_op_launch_info(A, op, k, ldx, ldy, nullptr, info);
+    BMSP_API_END
+}
+
 int bmsp_sddmm(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void *d_Y, int64_t ldy, int k, double alpha, double beta, int flags,
                int out_transposed, void *stream, bmsp_matrix_t *out)
 {

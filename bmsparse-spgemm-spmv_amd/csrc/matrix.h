@@ -98,6 +98,10 @@ struct bmsp_matrix_s {
     // bmsp_spmv_op: the view per op (0 = N, 1 = T), built on first use; the sum of a layout-0 matrix under op N before its epilogue
     bmsp_spmv_op_view spmv_op_views[2];
     void *spmv_op_tmp = nullptr;
+    // bmsp_spmm_op (spmm_op.hip): 8 * k accumulators per scratch slot of the views' split blocks, and the sum of a layout-0 matrix under
+    // op N before its epilogue; both grow to the largest call seen and go with the views (drop_spmv_op_views)
+    void *spmm_op_scratch = nullptr, *spmm_op_tmp = nullptr;
+    int64_t spmm_op_scratch_elems = 0, spmm_op_tmp_elems = 0;
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -269,6 +273,31 @@ void spmv_op_launch_info(bmsp_matrix_s *A, int op, hipStream_t st, bmsp_spmv_op_
 void spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
                         int64_t *split_blocks, int64_t *slots);
 void drop_spmv_op_views(bmsp_matrix_s *m);
+// what bmsp_spmm_op shares with bmsp_spmv_op: the argument checks (`what` names the call in the messages), the lengths of op(A)'s input and
+// output, the element size of the vectors that go with A, the cached view of (A, op) -- built if it is missing, which synchronises `st`
+// -- and the epilogue
+void spmv_op_check_matrix(const bmsp_matrix_s *A, const char *what);
+int64_t spmv_op_out_blocks(const bmsp_matrix_s *A, int op);
+int64_t spmv_op_out_length(const bmsp_matrix_s *A, int op);
+int64_t spmv_op_in_length(const bmsp_matrix_s *A, int op);
+size_t spmv_op_vector_size(const bmsp_matrix_s *A);
+bmsp_spmv_op_view &spmv_op_ensure_view(bmsp_matrix_s *A, int op, hipStream_t st);
+#ifdef __HIPCC__
+// u_j = fl(alpha * t) when beta == 0 (u is not read), else fl(fl(alpha * t) + fl(beta * u_j)): never contracted (add.hip's scaled_sum)
+template <typename R>
+__device__ __forceinline__ R spmv_op_epilogue(R alpha, R t, R beta, const R *u, int64_t j)
+{
+#pragma clang fp contract(off)
+    const R x = alpha * t;
+    if (beta == R(0)) return x;
+    const R y = beta * u[j];
+    return x + y;
+}
+#endif
+// spmm_op.hip: Y = alpha * op(A) * X + beta * Y for k vectors and either tile layout; what that call launches
+void spmm_op_check_args(int op, int k, int64_t ldx, int64_t ldy);
+void spmm_op(bmsp_matrix_s *A, int op, double alpha, const void *X, int64_t ldx, double beta, void *Y, int64_t ldy, int k, hipStream_t st);
+void spmm_op_launch_info(bmsp_matrix_s *A, int op, int k, int64_t ldx, int64_t ldy, hipStream_t st, bmsp_spmm_op_info *info);
 void spmm(bmsp_matrix_s *A, const void *X, int64_t ldx, void *Y, int64_t ldy, int k, hipStream_t st);
 void spmm_launch_info(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStream_t st, char *kernel, size_t kernel_cap);
 void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **C, int mode, int tc_version, int verbose, hipStream_t st,

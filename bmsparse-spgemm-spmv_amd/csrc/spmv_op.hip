@@ -35,17 +35,6 @@ constexpr uint32_t kWhole = ~0u;  // an item's scratch slot when it is a whole o
 constexpr int64_t kSplitDefault = 64;  // tiles per item (BMSP_SPMV_OP_SPLIT)
 constexpr int64_t kSlotsTiles = 6;     // SLOTS = 8 from this mean number of tiles per output block (BMSP_SPMV_OP_SLOTS)
 
-// u_j = fl(alpha * t) when beta == 0 (u is not read), else fl(fl(alpha * t) + fl(beta * u_j)): never contracted (add.hip's scaled_sum)
-template <typename R>
-__device__ __forceinline__ R epilogue(R alpha, R t, R beta, const R *u, int64_t j)
-{
-#pragma clang fp contract(off)
-    const R x = alpha * t;
-    if (beta == R(0)) return x;
-    const R y = beta * u[j];
-    return x + y;
-}
-
 template <typename S, bool MINOR, int SLOTS>
 __global__ __launch_bounds__(kThreads) void spmv_op_sweep_kernel(const uint4 *__restrict__ recs, const uint4 *__restrict__ items,
                                                                  uint64_t n_items, const S *__restrict__ vals, const S *__restrict__ v,
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void spmv_op_sweep_kernel(const uint4 *__
         return;
     }
     const int64_t o = (int64_t)it.x * 8 + j;
-    if (o < out_len) u[o] = epilogue<F>(alpha, acc, beta, u, o);  // (the ragged last block)
+    if (o < out_len) u[o] = spmv_op_epilogue<F>(alpha, acc, beta, u, o);  // (the ragged last block)
 }
 
 // folds: {output block, first scratch slot, parts} per split block; the parts are added in item order
@@ -112,14 +101,14 @@ __global__ __launch_bounds__(kThreads) void spmv_op_fold_kernel(const uint32_t *
     R acc = s[0];
     for (uint32_t p = 1; p < parts; p++) acc += s[(uint64_t)p * 8];
     const int64_t o = (int64_t)block * 8 + j;
-    if (o < out_len) u[o] = epilogue<R>(alpha, acc, beta, u, o);
+    if (o < out_len) u[o] = spmv_op_epilogue<R>(alpha, acc, beta, u, o);
 }
 
 template <typename R>
 __global__ __launch_bounds__(kThreads) void spmv_op_epilogue_kernel(const R *__restrict__ t, R alpha, R beta, R *u, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < n) u[i] = epilogue<R>(alpha, t[i], beta, u, i);
+    if (i < n) u[i] = spmv_op_epilogue<R>(alpha, t[i], beta, u, i);
 }
 
 // ---- the view --------------------------------------------------------------------------------------------------------------------------
@@ -164,25 +153,27 @@ int64_t split_from_env()
 
 size_t round16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-int64_t out_blocks(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_block_cols() : A->num_block_rows(); }
-int64_t out_length(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_cols : A->num_rows; }
-int64_t in_length(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_rows : A->num_cols; }
-size_t vector_size(const bmsp_matrix_s *A) { return A->dtype == BMSP_F64 ? 8 : 4; }
+}  // namespace
 
-void check_matrix(const bmsp_matrix_s *A)
+int64_t spmv_op_out_blocks(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_block_cols() : A->num_block_rows(); }
+int64_t spmv_op_out_length(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_cols : A->num_rows; }
+int64_t spmv_op_in_length(const bmsp_matrix_s *A, int op) { return op == BMSP_OP_T ? A->num_rows : A->num_cols; }
+size_t spmv_op_vector_size(const bmsp_matrix_s *A) { return A->dtype == BMSP_F64 ? 8 : 4; }
+
+void spmv_op_check_matrix(const bmsp_matrix_s *A, const char *what)
 {
-    refuse_view(A, "spmv_op");
-    if (A->block_num >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "spmv_op: more than 2^32 tiles");
-    if (A->nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "spmv_op: nnz %lld exceeds the 32-bit value offsets of the tile records", (long long)A->nnz);
+    refuse_view(A, what);
+    if (A->block_num >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "%s: more than 2^32 tiles", what);
+    if (A->nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "%s: nnz %lld exceeds the 32-bit value offsets of the tile records", what, (long long)A->nnz);
 }
 
 // builds the view of (A, op) if it is missing: synchronises `st` (the block pointer is read back for the item planner)
-bmsp_spmv_op_view &ensure_view(bmsp_matrix_s *A, int op, hipStream_t st)
+bmsp_spmv_op_view &spmv_op_ensure_view(bmsp_matrix_s *A, int op, hipStream_t st)
 {
     bmsp_spmv_op_view &w = A->spmv_op_views[op];
     if (w.mem) return w;
     const uint64_t nb = (uint64_t)A->block_num;
-    const int64_t blocks = out_blocks(A, op);
+    const int64_t blocks = spmv_op_out_blocks(A, op);
     TileSort ts;  // sort temporaries (op T): transpose_matrix's sort
     DevBuf<uint32_t> tptr;
     const uint64_t *sorted = nullptr;
@@ -212,7 +203,7 @@ bmsp_spmv_op_view &ensure_view(bmsp_matrix_s *A, int op, hipStream_t st)
     nw.off_items = nw.off_ptr + (op == BMSP_OP_T ? round16(4 * ((size_t)blocks + 1)) : 0);
     nw.off_folds = nw.off_items + 16 * (size_t)n_items;
     nw.off_scratch = round16(nw.off_folds + 12 * (size_t)split_blocks);
-    nw.bytes = nw.off_scratch + 8 * vector_size(A) * (size_t)slots;
+    nw.bytes = nw.off_scratch + 8 * spmv_op_vector_size(A) * (size_t)slots;
     DevBuf<char> mem(nw.bytes);
     device_for_each(PackRecords{map, sorted, A->keys, A->bmps, A->offsets, (uint4 *)mem.p}, nb, st);
     if (op == BMSP_OP_T) BMSP_HIP(hipMemcpyAsync(mem.p + nw.off_ptr, ptr, 4 * ((size_t)blocks + 1), hipMemcpyDeviceToDevice, st));
@@ -223,6 +214,8 @@ bmsp_spmv_op_view &ensure_view(bmsp_matrix_s *A, int op, hipStream_t st)
     w = nw;
     return w;
 }
+
+namespace {
 
 int slots_for(const bmsp_matrix_s *A, const bmsp_spmv_op_view &w)
 {
@@ -273,7 +266,7 @@ void spmv_plain(bmsp_matrix_s *A, double alpha, const void *v, double beta, void
         spmv(A, v, u, BMSP_SPMV_DEFAULT, st);
         return;
     }
-    if (!A->spmv_op_tmp) A->spmv_op_tmp = pool_alloc(vector_size(A) * (size_t)(A->num_rows ? A->num_rows : 1));
+    if (!A->spmv_op_tmp) A->spmv_op_tmp = pool_alloc(spmv_op_vector_size(A) * (size_t)(A->num_rows ? A->num_rows : 1));
     spmv(A, v, A->spmv_op_tmp, BMSP_SPMV_DEFAULT, st);
     if (f64) launch_epilogue<double>(A->spmv_op_tmp, alpha, beta, u, A->num_rows, st);
     else launch_epilogue<float>(A->spmv_op_tmp, alpha, beta, u, A->num_rows, st);
@@ -323,15 +316,15 @@ void spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint
 void spmv_op(bmsp_matrix_s *A, int op, double alpha, const void *v, double beta, void *u, hipStream_t st)
 {
     spmv_op_check_op(op);
-    check_matrix(A);
+    spmv_op_check_matrix(A, "spmv_op");
     if (op == BMSP_OP_N && !A->transposed) {
         spmv_plain(A, alpha, v, beta, u, st);
         return;
     }
-    const bmsp_spmv_op_view &w = ensure_view(A, op, st);
+    const bmsp_spmv_op_view &w = spmv_op_ensure_view(A, op, st);
     if (w.items == 0) return;  // no output
     const int slots = slots_for(A, w);
-    const int64_t out_len = out_length(A, op);
+    const int64_t out_len = spmv_op_out_length(A, op);
     const bool minor = (op == BMSP_OP_T) != (A->transposed != 0);
     dispatch_dtype(A->dtype, [&](auto s) {
         using S = decltype(s);
@@ -346,16 +339,16 @@ void spmv_op(bmsp_matrix_s *A, int op, double alpha, const void *v, double beta,
 void spmv_op_launch_info(bmsp_matrix_s *A, int op, hipStream_t st, bmsp_spmv_op_info *info)
 {
     spmv_op_check_op(op);
-    check_matrix(A);
+    spmv_op_check_matrix(A, "spmv_op");
     memset(info, 0, sizeof *info);
     if (op == BMSP_OP_N && !A->transposed) {
         char name[48];
         spmv_launch_info(A, BMSP_SPMV_DEFAULT, st, name, sizeof name, &info->compulsory_bytes, nullptr);
         snprintf(info->kernel, sizeof info->kernel, "bmsp_spmv: %s", name);
-        info->view_bytes = A->spmv_op_tmp ? (int64_t)vector_size(A) * A->num_rows : 0;
+        info->view_bytes = A->spmv_op_tmp ? (int64_t)spmv_op_vector_size(A) * A->num_rows : 0;
         return;
     }
-    const bmsp_spmv_op_view &w = ensure_view(A, op, st);
+    const bmsp_spmv_op_view &w = spmv_op_ensure_view(A, op, st);
     const bool minor = (op == BMSP_OP_T) != (A->transposed != 0);
     info->slots = slots_for(A, w);
     info->items = w.items;
@@ -366,8 +359,8 @@ void spmv_op_launch_info(bmsp_matrix_s *A, int op, hipStream_t st, bmsp_spmv_op_
         return;
     }
     snprintf(info->kernel, sizeof info->kernel, "spmv_op_sweep_kernel<%s, %d>", minor ? "MINOR" : "MAJOR", info->slots);
-    const int64_t es = (int64_t)dtype_size(A->dtype), as = (int64_t)vector_size(A);
-    info->compulsory_bytes = 16 * A->block_num + es * A->nnz + 16 * w.items + es * in_length(A, op) + as * out_length(A, op) +
+    const int64_t es = (int64_t)dtype_size(A->dtype), as = (int64_t)spmv_op_vector_size(A);
+    info->compulsory_bytes = 16 * A->block_num + es * A->nnz + 16 * w.items + es * spmv_op_in_length(A, op) + as * spmv_op_out_length(A, op) +
                              2 * 8 * as * w.slots + 12 * w.split_blocks;
 }
 

@@ -37,7 +37,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -73,6 +73,16 @@ class PruneStats(C.Structure):
 class SpmvOpInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("slots", C.c_int), ("items", C.c_int64), ("split_blocks", C.c_int64), ("view_bytes", C.c_int64),
                 ("compulsory_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
+class SpmmOpInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("col_chunks", C.c_int), ("items", C.c_int64), ("split_blocks", C.c_int64),
+                ("view_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("compulsory_bytes", C.c_int64)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
@@ -163,6 +173,8 @@ def lib():
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
         L.bmsp_spmm_launch_info.argtypes = [vp, i, i64, i64, C.c_char_p, C.c_size_t]
+        L.bmsp_spmm_op.argtypes = [vp, i, C.c_double, vp, i64, C.c_double, vp, i64, i, vp]
+        L.bmsp_spmm_op_launch_info.argtypes = [vp, i, i, i64, i64, p(SpmmOpInfo)]
         L.bmsp_spgemm.argtypes = [vp, vp, p(vp), i, i, i, vp, p(SpgemmStats)]
         L.bmsp_spgemm_symbolic.argtypes = [vp, vp, p(vp), i, i, vp, p(SpgemmStats)]
         L.bmsp_spgemm_numeric.argtypes = [vp, vp, vp, i, vp, p(SpgemmStats)]
@@ -445,6 +457,14 @@ class BmSpMatrix:
         """alpha * this^T * v + beta * u without a transposed copy: pybmsp.spmv_op(op="T")"""
         return spmv_op(self, v, "T", alpha, beta, u, stream)
 
+    def matmat(self, X, k, alpha=1.0, beta=0.0, Y=None, ldx=None, ldy=None, stream=None):
+        """alpha * this * X + beta * Y for k vectors, whatever the tile layout: pybmsp.spmm_op(op="N")"""
+        return spmm_op(self, X, k, "N", alpha, beta, Y, ldx, ldy, stream)
+
+    def rmatmat(self, X, k, alpha=1.0, beta=0.0, Y=None, ldx=None, ldy=None, stream=None):
+        """alpha * this^T * X + beta * Y for k vectors without a transposed copy: pybmsp.spmm_op(op="T")"""
+        return spmm_op(self, X, k, "T", alpha, beta, Y, ldx, ldy, stream)
+
     def sddmm(self, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, transposed=None, ldx=None, ldy=None, stream=None):
         """alpha * (X . Y^T) on this matrix's pattern (+ beta * this, or * this) as a new matrix: pybmsp.sddmm"""
         return sddmm(self, X, Y, k, alpha, beta, mul_s, transposed, ldx, ldy, stream)
@@ -703,6 +723,34 @@ def spmm_launch_info(A, k, ldx=None, ldy=None):
     name = C.create_string_buffer(160)
     check(lib().bmsp_spmm_launch_info(A.h, int(k), int(k if ldx is None else ldx), int(k if ldy is None else ldy), name, 160))
     return name.value.decode()
+
+
+def spmm_op(A, X, k, op="N", alpha=1.0, beta=0.0, Y=None, ldx=None, ldy=None, stream=None):
+    """Y = alpha * op(A) * X + beta * Y for k vectors (bmsp_spmm_op), op "N" or "T", A in either tile layout.  X: DeviceArray of A's dtype,
+    row-major num_cols ("N") / num_rows ("T") x k at leading dimension ldx (default k); Y: DeviceArray (float32, float64 for F64), row-major
+    output length x k at leading dimension ldy (default k), made when None (beta must then be 0).  Returns Y.  Asynchronous on `stream`
+    once the cached view of (A, op) and its scratch exist."""
+    o = _op(op)
+    if Y is None and beta != 0:
+        raise ValueError("beta != 0 needs Y")
+    i = A.info()
+    k = int(k)
+    ldx = k if ldx is None else int(ldx)
+    ldy = k if ldy is None else int(ldy)
+    n_out = i["num_cols"] if o == OP_T else i["num_rows"]
+    if Y is None:
+        Y = DeviceArray(n_out * max(ldy, 0), OUT_DTYPE[i["dtype"]])
+    check(lib().bmsp_spmm_op(A.h, o, float(alpha), X.ptr, ldx, float(beta), Y.ptr, ldy, k, stream))
+    return Y
+
+
+def spmm_op_launch_info(A, op, k, ldx=None, ldy=None):
+    """{"kernel", "lanes", "col_chunks", "items", "split_blocks", "view_bytes", "scratch_bytes", "compulsory_bytes"} of the launch
+    spmm_op(A, X, k, op) makes; builds the cached view of (A, op) if it is missing (bmsp_spmm_op_launch_info)."""
+    o = _op(op)
+    info = SpmmOpInfo()
+    check(lib().bmsp_spmm_op_launch_info(A.h, o, int(k), int(k if ldx is None else ldx), int(k if ldy is None else ldy), C.byref(info)))
+    return info.as_dict()
 
 
 def _sddmm_args(S, X, Y, k, ldx, ldy, mul_s):

@@ -307,6 +307,17 @@ template <class ValueIn, class ValueOut> inline void bmSparse_SpMM(bmSpMatrix<Va
     bmsp::check(bmsp_synchronize());
 }
 
+/* Y = alpha * op(A) * X + beta * Y for k vectors (bmsp_spmm_op), op = BMSP_OP_N or BMSP_OP_T, A in either tile layout: the transposed
+ * multi-vector product without a transposed copy.  X (input length of op(A) x k, A's value type, leading dimension ldx) and Y (output
+ * length x k; float, double for double; leading dimension ldy) are row-major device pointers; synchronous like bmSparse_SpMV. */
+template <class ValueIn>
+inline void bmSparse_SpMM_op(bmSpMatrix<ValueIn> &A, int op, double alpha, const ValueIn *X, int64_t ldx, double beta,
+                             typename bmsp::vector_of<ValueIn>::type *Y, int64_t ldy, int k)
+{
+    bmsp::check(bmsp_spmm_op(A.handle(), op, alpha, X, ldx, beta, Y, ldy, k, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+
 /* src/bmSparse_SPGEMM.cu:827-1223.  `mode` is the reference's `segmented` flag (declared bool there). */
 template <class valueIn, class valueOut>
 inline void bmSparse_mult(bmSpMatrix<valueIn> &A, bmSpMatrix<valueIn> &B, bmSpMatrix<valueOut> &C, bool mode, bool VERBOSE, long tc_version,

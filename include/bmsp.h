@@ -422,6 +422,55 @@ int bmsp_spmm(bmsp_matrix_t A, const void *d_X, int64_t ldx, void *d_Y, int64_t 
  * function the launcher itself calls.  Reporting only (tests pin kernels with it). */
 int bmsp_spmm_launch_info(bmsp_matrix_t A, int k, int64_t ldx, int64_t ldy, char *kernel_name, size_t kernel_name_cap);
 
+/* Y = alpha * op(A) * X + beta * Y for k vectors at once, op(A) = A (BMSP_OP_N) or A^T (BMSP_OP_T), for a matrix in EITHER tile layout
+ * -- the multi-vector form of bmsp_spmv_op: the gradient of bmsp_spmm with respect to X (A^T * G) without bmsp_matrix_transpose and a
+ * second copy of the matrix, the multi-vector product of a column-major matrix (bmsp_spmm refuses those), and a scaled accumulate.
+ * Nothing in the reference is replaced: its one product is u = A * v on a row-major A (src/bmSparse_SPMV.cu:191-230; bmsp_spmv above).
+ *   Operands: X is in_len x k, row-major, leading dimension ldx >= k, elements of A's dtype (fp16 for F16); in_len = num_cols for N,
+ *       num_rows for T.  Y is out_len x k, row-major, leading dimension ldy >= k, float for F32 / F16 and double for F64.  Matrix
+ *       coordinates, whatever the tile layout.  Pointers need the alignment of their element type and no more.
+ *   Read and written: every Y[i][c], i < out_len, c < k, is written.  The padding columns k <= c < ld of X are never read into a result,
+ *       those of Y never written.  No row of X at or beyond in_len is read (the ragged last block).
+ *   Sum: t[i][c] = the sum over the stored entries of row i of op(A) of a * X[col][c] -- bmsp_spmv's rule, stored entries only: an X
+ *       element at an input index where output row i stores nothing never reaches t[i][c], inside a stored tile too, and a stored value
+ *       is always multiplied (a stored 0 against Inf is NaN; Inf and NaN propagate as IEEE says).  Products and sums in fp32 (double for
+ *       F64), F16 operands widened exactly, subnormals kept; +0 for a row without stored entries.  Contraction into fused multiply-adds
+ *       is allowed and the order of summation is the implementation's, but t is a pure function of A's arrays, X, k, the strides and the
+ *       switches below: no floating-point atomic anywhere, no dependence on scheduling, two calls with the same inputs give the same bits.
+ *   Epilogue: bmsp_spmv_op's, element by element.  alpha and beta are rounded once to the vector type.  beta == 0 (after that rounding):
+ *       Y = fl(alpha * t); Y is not read, a NaN in it does not propagate.  Otherwise Y = fl(fl(alpha * t) + fl(beta * Y)), each operation
+ *       rounded on its own, never contracted.  alpha == 0 is not special-cased.
+ *   (N, row-major A) is bmsp_spmm's case: t is exactly what bmsp_spmm(A, X, ldx, ., ., k) writes; with alpha == 1 and beta == 0 the call
+ *       IS that call into Y, otherwise bmsp_spmm runs into a temporary kept on the handle (out_len x k, unit stride, sized for the largest
+ *       out_len * k seen on the handle) and one strided epilogue kernel follows.  bmsp_spmm's synchronisation rules apply to this case.
+ *   The other three cases sweep the cached view of (A, op) that bmsp_spmv_op builds: the same records, items and fold list, ONE view per
+ *       op shared by both calls, dropped by the same events (bmsp_matrix_invalidate(A, 1), bmsp_matrix_free; value-only updates keep it).
+ *       The items of an output block of more than SPLIT tiles need 8 * k accumulators per scratch slot: a buffer on the handle that grows
+ *       when slots * k exceeds what any earlier call needed and is freed with the views.  Values are read from A's value array at every
+ *       call.
+ *   Asynchronous on `stream` with two exceptions, both of which synchronise it: the one-time build of the view, and a call that has to
+ *       grow the scratch or the temporary (the old buffer goes back to the pool only after the work enqueued on it has finished).  One
+ *       stream per handle at a time.  A's four arrays are not modified.
+ *   Switches, read per call: BMSP_SPMM_OP_LANES=8/16/32/64 forces W, the lanes (= columns of X and Y) of one tile slot of a wave; by default
+ *       the smallest of them that is >= min(k, 64).  Columns beyond W go to further column chunks.  BMSP_SPMV_OP_SPLIT belongs to the
+ *       shared view and keeps its meaning (read when a view is built).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles: op not 0 / 1; k < 1; ldx < k or ldy < k; null
+ *   A, d_X, d_Y, info; row-panel views.  BMSP_ERR_LIMIT: 2^32 tiles or values or more; slots * 8 * k scratch elements beyond 2^32 - 1. */
+int bmsp_spmm_op(bmsp_matrix_t A, int op, double alpha, const void *d_X, int64_t ldx, double beta, void *d_Y, int64_t ldy, int k, void *stream);
+/* What bmsp_spmm_op(A, op, ., X, ldx, ., Y, ldy, k) launches -- the launcher's own decisions, made by the function the launcher calls:
+ * the kernel by name ("spmm_op_sweep_kernel<MINOR, 16>": MAJOR / MINOR as for bmsp_spmv_op, then W; "bmsp_spmm: <bmsp_spmm_launch_info's
+ * name>" for (N, row-major A) -- bmsp_spmm into Y at ldy, the alpha == 1, beta == 0 call --, which has no view: lanes, col_chunks, items, split_blocks 0, view_bytes = scratch_bytes = the temporary
+ * once it exists; "none (no output)"), W (`lanes`), the column chunks ceil(k / W), the work items, the split output blocks, the bytes
+ * the view holds, the bytes of the scratch this call needs (8 * k * slots accumulators) and the bytes the launch must move.
+ *   Counting rule for compulsory_bytes (the view cases; 0 for (N, row-major A), whose kernels bmsp_spmm_launch_info names): per column
+ *       chunk the 16 B record of every tile and the 16 B of every work item; per column chunk every stored value once (element size of
+ *       A's dtype); k elements of X for every X row a tile reads, counted once per tile that reads it (the rows of the tile's input side
+ *       that hold a stored value, not once per matrix); Y written: out_len * k accumulator elements; Y read: NOT counted -- the info call
+ *       has no beta and reports the beta == 0 launch, a beta != 0 launch moves out_len * k accumulator elements more; per scratch slot
+ *       its 8 * k accumulators stored and read back; the fold list, 12 B per split block.  Builds the view if it is missing (it synchronises) and reads A's bitmaps back for the X rows.  Reporting only. */
+typedef struct { char kernel[64]; int lanes, col_chunks; int64_t items, split_blocks, view_bytes, scratch_bytes, compulsory_bytes; } bmsp_spmm_op_info;
+int bmsp_spmm_op_launch_info(bmsp_matrix_t A, int op, int k, int64_t ldx, int64_t ldy, bmsp_spmm_op_info *info);
+
 /* per-stage figures of one product: the lines the reference prints when VERBOSE
  * (src/bmSparse_SPGEMM.cu:849-1220) plus what the roofline needs. */
 typedef struct {
