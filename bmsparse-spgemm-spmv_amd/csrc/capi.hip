@@ -677,6 +677,41 @@ int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int
     BMSP_API_END
 }
 
+int bmsp_spgemm_masked(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, double alpha, double beta, int flags, int out_transposed, void *stream,
+                       bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    spgemm_masked_check_args(beta, flags, out_transposed);
+    need(A, "matrix A"); need(B, "matrix B"); need(M, "matrix M"); need(out, "out");
+    spgemm_masked_check_matrices(A, B, M, nullptr);
+    load_kernels();
+    *out = spgemm_masked_matrix(A, B, M, alpha, beta, flags, out_transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spgemm_masked_values(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, double alpha, double beta, int flags, bmsp_matrix_t out,
+                              void *stream)
+{
+    BMSP_API_BEGIN
+    spgemm_masked_check_args(beta, flags, 0);
+    need(A, "matrix A"); need(B, "matrix B"); need(M, "matrix M"); need(out, "matrix out");
+    spgemm_masked_check_matrices(A, B, M, out);
+    load_kernels();
+    spgemm_masked_values_into(A, B, M, alpha, beta, flags, out, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spgemm_masked_launch_info(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, int out_transposed, bmsp_spgemm_masked_info *info)
+{
+    BMSP_API_BEGIN
+    spgemm_masked_check_args(0.0, 0, out_transposed);
+    need(A, "matrix A"); need(B, "matrix B"); need(M, "matrix M"); need(info, "info");
+    spgemm_masked_check_matrices(A, B, M, nullptr);
+    load_kernels();
+    spgemm_masked_launch_info(A, B, M, out_transposed, info);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

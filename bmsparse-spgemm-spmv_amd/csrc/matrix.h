@@ -259,6 +259,16 @@ bmsp_matrix_s *sddmm_matrix(bmsp_matrix_s *S, const void *X, int64_t ldx, const 
 void sddmm_values_into(bmsp_matrix_s *S, const void *X, int64_t ldx, const void *Y, int64_t ldy, int k, double alpha, double beta, int flags,
                        bmsp_matrix_s *out, hipStream_t st);
 void sddmm_launch_info(bmsp_matrix_s *S, int k, int64_t ldx, int64_t ldy, int out_transposed, bmsp_sddmm_info *info);
+// spgemm_masked.hip: the masked sparse product alpha * (A * B) on M's pattern (+ beta * M, or * M) as a new matrix (tiles in layout
+// out_transposed) or into M itself / a matrix made from M by spgemm_masked_matrix, sddmm_matrix, scale_matrix or a layout conversion; what
+// that call launches.  Builds A's block-row pointer and B's op-T view if they are missing (the latter synchronises `st`).
+void spgemm_masked_check_args(double beta, int flags, int out_transposed);
+void spgemm_masked_check_matrices(const bmsp_matrix_s *A, const bmsp_matrix_s *B, const bmsp_matrix_s *M, const bmsp_matrix_s *out);
+bmsp_matrix_s *spgemm_masked_matrix(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *M, double alpha, double beta, int flags,
+                                    int out_transposed, hipStream_t st);
+void spgemm_masked_values_into(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *M, double alpha, double beta, int flags, bmsp_matrix_s *out,
+                               hipStream_t st);
+void spgemm_masked_launch_info(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *M, int out_transposed, bmsp_spgemm_masked_info *info);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

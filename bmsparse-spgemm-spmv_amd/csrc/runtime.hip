@@ -190,6 +190,7 @@ void warm_prune(hipStream_t st);
 void warm_diag(hipStream_t st);
 void warm_spmv_op(hipStream_t st);
 void warm_sddmm(hipStream_t st);
+void warm_spgemm_masked(hipStream_t st);
 void warm_spmm_op(hipStream_t st);
 
 void *host_slot_acquire();
@@ -225,6 +226,7 @@ void load_kernels()
     warm_diag(nullptr);
     warm_spmv_op(nullptr);
     warm_sddmm(nullptr);
+    warm_spgemm_masked(nullptr);
     warm_spmm_op(nullptr);
     // the first pinned host page and the first device-to-host copy of a process cost ~15 ms (measured inside the first product's T_1):
     // taken here too, with a copy through the slot

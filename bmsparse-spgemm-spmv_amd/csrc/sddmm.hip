@@ -30,8 +30,6 @@ constexpr int kRun = 8;            // tiles per wave of the tile kernel
 constexpr int kPairs = kRun / 2;   // MFMA accumulators per wave
 constexpr int kFillThreshold = 6;  // mean values per tile from which the tile kernel is the default (measured: DESIGN section 4 "SDDMM")
 
-enum { kModeAlpha = 0, kModeAdd = 1, kModeMul = 2 };  // c = alpha*d | alpha*d + beta*s | alpha*d * s
-
 typedef _Float16 half8_d __attribute__((ext_vector_type(8)));
 typedef float float4_d __attribute__((ext_vector_type(4)));
 typedef double double2_d __attribute__((ext_vector_type(2)));
@@ -60,20 +58,6 @@ struct Operand<double> {
 
 __device__ __forceinline__ float fma_f(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_f(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// c from the dot product d and the stored s (read only when mode says so)
-template <typename F>
-__device__ __forceinline__ F epilogue(F d, F alpha, F beta, F s, int mode)
-{
-#pragma clang fp contract(off)
-    const F t = alpha * d;
-    if (mode == kModeMul) return t * s;
-    if (mode == kModeAdd) {
-        const F u = beta * s;
-        return t + u;
-    }
-    return t;
-}
 
 // x . y over k elements: element t goes into partial sum t mod NV, the partial sums are added in index order (vec: 16-byte loads)
 template <typename S>
@@ -339,21 +323,13 @@ void launch_tile(const bmsp_matrix_s *Sm, bmsp_matrix_s *out, const void *X, int
     BMSP_CHECK_LAUNCH();
 }
 
-// alpha and beta rounded once to the arithmetic type decide the form: beta == 0 there means s is not read
-int epilogue_mode(bmsp_dtype dtype, double beta, int flags)
-{
-    if (flags & BMSP_SDDMM_MUL_S) return kModeMul;
-    const bool zero = dtype == BMSP_F64 ? beta == 0.0 : (float)beta == 0.0f;
-    return zero ? kModeAlpha : kModeAdd;
-}
-
 // out's values from S, X and Y through out's layout; out has S's tile order (out == S: in place)
 void sddmm_pass(const bmsp_matrix_s *S, bmsp_matrix_s *out, const void *X, int64_t ldx, const void *Y, int64_t ldy, int k, double alpha,
                 double beta, int flags, hipStream_t st)
 {
     if (out->block_num == 0 || out->nnz == 0) return;
     const Choice ch = choose_kernel(S, X, ldx, Y, ldy);
-    const int mode = epilogue_mode(S->dtype, beta, flags);
+    const int mode = epilogue_mode(S->dtype, beta, (flags & BMSP_SDDMM_MUL_S) != 0);
     if (ch.tile) {
         if (S->dtype == BMSP_F16) launch_tile<uint16_t>(S, out, X, ldx, Y, ldy, k, alpha, beta, mode, st);
         else launch_tile<float>(S, out, X, ldx, Y, ldy, k, alpha, beta, mode, st);

@@ -16,13 +16,14 @@ namespace bmsp {
 // eight lanes from there (banded: 58).  G = 1: a lane walks its tile's few values; G = 8: lane t takes byte t of the bitmap, consecutive
 // lanes on consecutive values of one segment (a wave per tile measured slower even on full tiles, DESIGN §4 "Transpose", where the
 // threshold was measured).  The environment variable `override_var` = 1 / 8 forces one (measurement and test switch, read per call).
-inline int lane_group(int64_t nnz, int64_t nb, const char *override_var)
+// `threshold`: the mean fill from which eight lanes are the default, for a pass that measured another one than the family's 6.
+inline int lane_group(int64_t nnz, int64_t nb, const char *override_var, int64_t threshold = 6)
 {
     if (const char *e = getenv(override_var)) {
         const int g = atoi(e);
         if (g == 1 || g == 8) return g;
     }
-    return nb == 0 || nnz < 6 * nb ? 1 : 8;
+    return nb == 0 || nnz < threshold * nb ? 1 : 8;
 }
 
 // Launches a pass over `tiles` tiles at g = 1 or 8 lanes per tile: launch(std::integral_constant<int, G>, grid) names the kernel
@@ -97,6 +98,31 @@ struct TileValue<double> {
     static __device__ __forceinline__ U abs_bits(double s) { return __builtin_bit_cast(uint64_t, s) & 0x7fffffffffffffffull; }
     static __device__ __forceinline__ double widen(double s) { return s; }
 };
+
+// The epilogue of the sampled products (sddmm.hip, spgemm_masked.hip): c from the dot product d and the stored value s of the pattern.
+enum { kModeAlpha = 0, kModeAdd = 1, kModeMul = 2 };  // c = alpha*d | alpha*d + beta*s | alpha*d * s
+
+// alpha and beta rounded once to the arithmetic type decide the form: beta == 0 there means s is not read
+inline int epilogue_mode(bmsp_dtype dtype, double beta, bool mul)
+{
+    if (mul) return kModeMul;
+    const bool zero = dtype == BMSP_F64 ? beta == 0.0 : (float)beta == 0.0f;
+    return zero ? kModeAlpha : kModeAdd;
+}
+
+// c from the dot product d and the stored s (read only when mode says so): each operation rounded on its own, never contracted
+template <typename F>
+__device__ __forceinline__ F epilogue(F d, F alpha, F beta, F s, int mode)
+{
+#pragma clang fp contract(off)
+    const F t = alpha * d;
+    if (mode == kModeMul) return t * s;
+    if (mode == kModeAdd) {
+        const F u = beta * s;
+        return t + u;
+    }
+    return t;
+}
 
 // first index in [lo, hi) whose key is >= k; [lo, hi) is a block-row's range of the cached block-row pointer
 __device__ __forceinline__ uint32_t lower_bound_key(const uint64_t *keys, uint32_t lo, uint32_t hi, uint64_t k)

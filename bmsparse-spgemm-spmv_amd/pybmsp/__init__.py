@@ -24,6 +24,7 @@ PRUNE_KEEP_DIAGONAL = 1
 SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
 OP_N, OP_T = 0, 1
 SDDMM_MUL_S = 1
+MASKED_MUL_M = 1
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
@@ -37,7 +38,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -95,6 +96,13 @@ class SddmmInfo(C.Structure):
 
     def as_dict(self):
         return {"kernel": self.kernel.decode(), "lanes": self.lanes, "compulsory_bytes": self.compulsory_bytes}
+
+
+class SpgemmMaskedInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("pairs", C.c_int64), ("view_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {"kernel": self.kernel.decode(), "lanes": self.lanes, "pairs": self.pairs, "view_bytes": self.view_bytes}
 
 
 class ShardStats(C.Structure):
@@ -172,6 +180,9 @@ def lib():
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
+        L.bmsp_spgemm_masked.argtypes = [vp, vp, vp, C.c_double, C.c_double, i, i, vp, p(vp)]
+        L.bmsp_spgemm_masked_values.argtypes = [vp, vp, vp, C.c_double, C.c_double, i, vp, vp]
+        L.bmsp_spgemm_masked_launch_info.argtypes = [vp, vp, vp, i, p(SpgemmMaskedInfo)]
         L.bmsp_spmm_launch_info.argtypes = [vp, i, i64, i64, C.c_char_p, C.c_size_t]
         L.bmsp_spmm_op.argtypes = [vp, i, C.c_double, vp, i64, C.c_double, vp, i64, i, vp]
         L.bmsp_spmm_op_launch_info.argtypes = [vp, i, i, i64, i64, p(SpmmOpInfo)]
@@ -472,6 +483,10 @@ class BmSpMatrix:
     def sddmm_(self, X, Y, k, alpha=1.0, beta=0.0, mul_s=False, ldx=None, ldy=None, stream=None):
         """the same into this matrix's own values (bmsp_sddmm_values with out == S)"""
         return sddmm_values(self, self, X, Y, k, alpha, beta, mul_s, ldx, ldy, stream)
+
+    def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
+        """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
+        return spgemm_masked(self, B, M, alpha, beta, mul_m, transposed, stream)
 
     def copy_values_from(self, src, stream=None):
         """re-gathers this matrix's values from `src`, which it was made from by transpose() / with_layout() (bmsp_matrix_copy_values)."""
@@ -795,6 +810,54 @@ def sddmm_launch_info(S, k, ldx=None, ldy=None, transposed=None):
     lay = S.info()["transposed"] if transposed is None else int(bool(transposed))
     info = SddmmInfo()
     check(lib().bmsp_sddmm_launch_info(S.h, k, k if ldx is None else int(ldx), k if ldy is None else int(ldy), lay, C.byref(info)))
+    return info.as_dict()
+
+
+def _spgemm_masked_args(A, B, M, beta, mul_m, out=None):
+    ia, ib, im = A.info(), B.info(), M.info()
+    if mul_m and beta != 0:
+        raise ValueError("beta must be 0 with mul_m (got %r)" % (beta,))
+    if ia["num_cols"] != ib["num_rows"]:
+        raise ValueError("A.num_cols (%d) != B.num_rows (%d)" % (ia["num_cols"], ib["num_rows"]))
+    if (im["num_rows"], im["num_cols"]) != (ia["num_rows"], ib["num_cols"]):
+        raise ValueError("M is %d x %d, A * B is %d x %d" % (im["num_rows"], im["num_cols"], ia["num_rows"], ib["num_cols"]))
+    if ia["dtype"] != ib["dtype"]:
+        raise ValueError("A and B differ in dtype (%d, %d)" % (ia["dtype"], ib["dtype"]))
+    if im["dtype"] != ia["dtype"] and not (ia["dtype"] == F16 and im["dtype"] == F32):
+        raise ValueError("M's dtype (%d) must be A's (%d), or F32 for F16 operands" % (im["dtype"], ia["dtype"]))
+    if out is not None and (out is A or out is B or (out.h is not None and out.h in (A.h, B.h))):
+        raise ValueError("out must not be A or B: the pass would read what it writes")
+    return im, MASKED_MUL_M if mul_m else 0
+
+
+def spgemm_masked(A, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
+    """The masked sparse product on M's pattern as a new matrix (bmsp_spgemm_masked): for every stored (i, j) of M,
+    alpha * sum_k a_ik * b_kj + beta * m_ij, or alpha * sum * m_ij with mul_m (beta must then be 0); the sum runs over the inner indices
+    both operands store, k ascending, one fused multiply-add per product.  A (m x n), B (n x p) and M (m x p) may have either tile layout
+    and may be the same matrix; M has A's dtype, or F32 for F16 operands.  The output has M's structure and dtype in layout `transposed`
+    (None: M's layout).  Asynchronous on `stream` once B's op-T view exists."""
+    im, flags = _spgemm_masked_args(A, B, M, beta, mul_m)
+    lay = im["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    check(lib().bmsp_spgemm_masked(A.h, B.h, M.h, float(alpha), float(beta), flags, lay, stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def spgemm_masked_values(out, A, B, M, alpha=1.0, beta=0.0, mul_m=False, stream=None):
+    """the values of spgemm_masked(A, B, M, ...) into `out`: M itself (in place) or a matrix made from M by spgemm_masked() / sddmm() /
+    scale() / with_layout(); never A or B (bmsp_spgemm_masked_values)."""
+    _, flags = _spgemm_masked_args(A, B, M, beta, mul_m, out)
+    check(lib().bmsp_spgemm_masked_values(A.h, B.h, M.h, float(alpha), float(beta), flags, out.h, stream))
+    return out
+
+
+def spgemm_masked_launch_info(A, B, M, transposed=None):
+    """{"kernel", "lanes", "pairs", "view_bytes"} of the launch spgemm_masked(A, B, M) makes; builds B's op-T view if it is missing
+    (bmsp_spgemm_masked_launch_info)."""
+    im, _ = _spgemm_masked_args(A, B, M, 0.0, False)
+    lay = im["transposed"] if transposed is None else int(bool(transposed))
+    info = SpgemmMaskedInfo()
+    check(lib().bmsp_spgemm_masked_launch_info(A.h, B.h, M.h, lay, C.byref(info)))
     return info.as_dict()
 
 

@@ -420,6 +420,28 @@ inline void bmSparse_sddmm_values(bmSpMatrix<valueType> &S, const valueType *X, 
     bmsp::check(bmsp_synchronize());
 }
 
+/* Masked SpGEMM (bmsp_spgemm_masked / bmsp_spgemm_masked_values): C = alpha * (A * B) on M's pattern + beta * M, or alpha * (A * B) * M
+ * under flags = BMSP_MASKED_MUL_M (beta must then be 0).  A, B and M may have either tile layout and may be the same matrix; M and C have
+ * A's value type, or float for half operands.  C receives M's structure in the layout asked for; the _values form writes into M itself (C
+ * is M) or into a C made from M by bmSparse_mult_masked, bmSparse_sddmm, bmSparse_scale or with_layout, never into A or B.  Synchronous
+ * like bmSparse_sddmm. */
+template <class valueIn, class valueOut>
+inline void bmSparse_mult_masked(bmSpMatrix<valueIn> &A, bmSpMatrix<valueIn> &B, bmSpMatrix<valueOut> &M, bmSpMatrix<valueOut> &C,
+                                 double alpha = 1.0, double beta = 0.0, int flags = 0, bool transposed_layout = false)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_spgemm_masked(A.handle(), B.handle(), M.handle(), alpha, beta, flags, transposed_layout ? 1 : 0, nullptr, &c));
+    bmsp::check(bmsp_synchronize());
+    C.reset(c);
+}
+template <class valueIn, class valueOut>
+inline void bmSparse_mult_masked_values(bmSpMatrix<valueIn> &A, bmSpMatrix<valueIn> &B, bmSpMatrix<valueOut> &M, bmSpMatrix<valueOut> &C,
+                                        double alpha = 1.0, double beta = 0.0, int flags = 0)
+{
+    bmsp::check(bmsp_spgemm_masked_values(A.handle(), B.handle(), M.handle(), alpha, beta, flags, C.handle(), nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+
 /* The same product sharded over one process per GPU (bmsp_spgemm_sharded): every rank passes the same A and B, multiplies
  * its block-row panel of A and returns the whole C. */
 template <class valueIn, class valueOut>

@@ -401,6 +401,62 @@ int bmsp_sddmm_values(bmsp_matrix_t S, const void *d_X, int64_t ldx, const void 
 typedef struct { char kernel[64]; int lanes; int64_t compulsory_bytes; } bmsp_sddmm_info;
 int bmsp_sddmm_launch_info(bmsp_matrix_t S, int k, int64_t ldx, int64_t ldy, int out_transposed, bmsp_sddmm_info *info);
 
+/* Masked SpGEMM, the product of two sparse matrices evaluated only on the pattern of a third (GraphBLAS mxm with a mask): for every stored
+ * coordinate (i, j) of M
+ *       c_ij = alpha * d_ij + beta * m_ij      or, under BMSP_MASKED_MUL_M,      c_ij = alpha * d_ij * m_ij,
+ *       d_ij = the sum over the inner indices k at which A stores (i, k) AND B stores (k, j) of a_ik * b_kj
+ * on the device (triangle counting (A * A) o A, a Galerkin product kept on a prescribed pattern instead of bmsp_spgemm followed by
+ * bmsp_matrix_prune, the residual of an incomplete factorisation on its pattern, masked attention with sparse factors).  Nothing in the
+ * reference is replaced: it has no such entry point.
+ *   Shapes and layouts: A is m x n, B is n x p, M is m x p, in matrix coordinates.  Each of the three may have either tile layout: an
+ *       operand in the "wrong" layout is read through the transposed bitmap, no conversion and no copy is made.  A, B and M may be the
+ *       same handle.
+ *   Dtypes: A and B share a dtype; M has that dtype, or F32 when A and B are F16 (what bmsp_spgemm returns for F16 operands); the output
+ *       has M's dtype.
+ *   Dot product: bmsp_spmv's stored-entries-only rule -- an unstored position never contributes (an Inf stored in A opposite a position B
+ *       does not store does not reach the result), a stored 0 does (0 * Inf = NaN).  The order is fixed: k ascending over the whole inner
+ *       dimension, one fused multiply-add per product, d = fma(a_ik, b_kj, d) starting from +0, in fp32 (double for F64).  F16 operands
+ *       are widened exactly, so their products are exact in fp32: these are the numerics of bmsp_spgemm's tc_version 1..4, NOT those of
+ *       tc_version 5 (V15) on F16, which rounds every product to fp16.  For finite F32 / F64 operands, alpha = 1 and beta = 0 the call
+ *       returns the values bmsp_spgemm(A, B, tc_version 5) stores at M's coordinates (the same chain of fused multiply-adds) and +0 at
+ *       coordinates the product does not hold; the sign of a zero result is not specified.  d is a pure function of the three matrices:
+ *       nothing in it depends on scheduling or on the lane switch below, two calls with the same inputs give the same bits.
+ *   Epilogue: bmsp_sddmm's, operation by operation.  alpha and beta are rounded once to the arithmetic type (fp32; double for F64); each
+ *       operation is rounded on its own, never contracted.  Default form c = fl(fl(alpha * d) + fl(beta * m)); with beta == 0 after that
+ *       rounding m is not read: c = fl(alpha * d), a NaN stored in M does not propagate.  BMSP_MASKED_MUL_M: c = fl(fl(alpha * d) * m);
+ *       beta must be 0.  An F16 output is rounded once more, round-to-nearest-even (it may overflow to +-Inf).  Subnormals are kept.
+ *   bmsp_spgemm_masked: `out` is a fresh pool-owned matrix of M's shape and dtype with tiles in layout out_transposed; its keys, bitmaps,
+ *       offsets and block-row pointer equal bmsp_matrix_convert_layout(M, out_transposed)'s bit for bit: every coordinate is kept, zeros
+ *       included.  The output remembers M as a bmsp_matrix_scale / bmsp_sddmm output does.
+ *   bmsp_spgemm_masked_values: the same value pass into an existing matrix.  out == M works in place.  Any other `out` must have been made
+ *       from M by this call, bmsp_sddmm, bmsp_matrix_scale or bmsp_matrix_convert_layout while M's STRUCTURE has not changed since;
+ *       anything else is BMSP_ERR_INVALID.  out == A or out == B is refused (the pass would read what it writes); M == A with a separate
+ *       `out` is the triangle-counting call.  Drops out's value-derived caches as bmsp_sddmm_values does.
+ *   A, B and M and their caches are not modified, except that A's block-row pointer and B's op-T view (the cached view of bmsp_spmv_op(B,
+ *       BMSP_OP_T): B's tiles in (block-column, block-row) order with a block-column pointer, structure only) are built if missing.
+ *   Synchronisation: the first call on a B without its op-T view builds the view and synchronises `stream`.  After that both calls are
+ *       asynchronous on `stream`: nothing is read back, no temporary is allocated.  The pass reads A's and B's value arrays at every call,
+ *       so value-only updates need no bmsp_matrix_invalidate; bmsp_matrix_invalidate(B, 1) drops the view.
+ *   Kernel: spgemm_masked_kernel (vector ALU), 1 or 8 lanes per M tile; a lane owns one byte of the output bitmap at a time and walks the
+ *       intersection of A's block-row with B's block-column in ascending inner index.  BMSP_MASKED_LANES=1/8 forces the lanes per tile
+ *       (read per call; default: eight at every fill, the measured choice -- see README).  An M tile whose two lists are both long
+ *       (hub x hub on a power-law matrix) is one lane group's serial chain.
+ *   bmsp_spgemm_masked_launch_info: the kernel by name ("spgemm_masked_kernel<1>" / "<8>", "none (empty mask)"), the lanes per M tile, the
+ *       bytes of B's view and `pairs`, the number of triples (M tile (I, J), K) for which A holds tile (I, K) and B holds tile (K, J) --
+ *       counted on the device by the walk the value kernel uses.  Builds the view if it is missing and synchronises.  Reporting only.
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, all before any device call: flags with unknown
+ *   bits; BMSP_MASKED_MUL_M with beta != 0; out_transposed not 0 / 1; null A, B, M, out, info; A.num_cols != B.num_rows or M not m x p;
+ *   dtype combinations other than the four above; row-panel views; out aliasing A or B.  BMSP_ERR_LIMIT: 2^32 tiles or values or more in
+ *   any operand. */
+#define BMSP_MASKED_MUL_M 1   /* flags bit 0: c = fl(fl(alpha*d) * m) instead of fl(fl(alpha*d) + fl(beta*m)); beta must be 0 */
+int bmsp_spgemm_masked(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, double alpha, double beta, int flags,
+                       int out_transposed, void *stream, bmsp_matrix_t *out);
+int bmsp_spgemm_masked_values(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, double alpha, double beta, int flags,
+                              bmsp_matrix_t out, void *stream);
+typedef struct { char kernel[64]; int lanes; int64_t pairs, view_bytes; } bmsp_spgemm_masked_info;
+int bmsp_spgemm_masked_launch_info(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t M, int out_transposed,
+                                   bmsp_spgemm_masked_info *info);
+
 /* SURVEY 8(f)3 -- Y = A * X for k vectors at once (what the reference's unfinished `batched` path points at,
  * src/bmSparse_SPMV.cu:84-150,191).  X is row-major num_cols x k with leading dimension ldx (elements of A's dtype),
  * Y row-major num_rows x k with leading dimension ldy (float, double for F64): one pass over A's tiles for all k.
