@@ -406,6 +406,7 @@ void free_matrix(bmsp_matrix_s *m)
     pool_free(m->tp_map);
     pool_free(m->add_map);
     drop_spmv_op_views(m);
+    drop_spsv_plans(m);
     free_matrix(m->shard_view);
     delete m;
 }
@@ -469,6 +470,7 @@ void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)
     pool_free(m->tp_map); m->tp_map = nullptr; m->tp_src_uid = 0; m->tp_permute = 0;
     pool_free(m->add_map); m->add_map = nullptr; m->add_a_uid = 0; m->add_b_uid = 0;
     drop_spmv_op_views(m);
+    drop_spsv_plans(m);
     free_matrix(m->shard_view); m->shard_view = nullptr; m->shard_world = 0; m->shard_rank = 0; m->shard_bounds.clear();
 }
 

@@ -712,6 +712,36 @@ int bmsp_spgemm_masked_launch_info(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix
     BMSP_API_END
 }
 
+int bmsp_spsv_analyse(bmsp_matrix_t A, int op, int fill, int diag, void *stream, bmsp_spsv_info *info)
+{
+    BMSP_API_BEGIN
+    spsv_check_args(op, fill, diag);
+    need(A, "matrix A");
+    spsv_check_matrix(A);
+    load_kernels();
+    spsv_analyse(A, op, fill, diag, as_stream(stream), info);
+    BMSP_API_END
+}
+
+int bmsp_spsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_b, void *d_x, void *stream)
+{
+    BMSP_API_BEGIN
+    spsv_check_args(op, fill, diag);
+    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
+    spsv_check_matrix(A);
+    load_kernels();
+    spsv(A, op, fill, diag, alpha, d_b, d_x, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
+                   uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
+{
+    BMSP_API_BEGIN
+    spsv_plan(ptr, other, blocks, lower, chain, level_of, order, level_ptr, segments, n_levels, n_segments);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

@@ -19,6 +19,17 @@ struct bmsp_spmv_op_view {
     int64_t blocks = 0, items = 0, split_blocks = 0, slots = 0;
 };
 
+// The cached plan of bmsp_spsv for one (op, fill) (spsv.hip), structure only: on the device the output blocks ordered by (level, index)
+// and the level pointer (one allocation); on the host the level pointer again and the launch schedule {first level, end level, kind (0 one
+// level kernel, 1 one chain kernel)}, three words per launch.  missing_diag_row: the first row below n whose diagonal entry A does not
+// store (-1: none) -- what a BMSP_DIAG_NON_UNIT call is refused for.
+struct bmsp_spsv_plan_s {
+    uint32_t *mem = nullptr;
+    size_t off_level_ptr = 0, bytes = 0;
+    int64_t blocks = 0, levels = 0, max_level_width = 0, chain_launches = 0, chained_levels = 0, chain = 0, missing_diag_row = -1;
+    std::vector<uint32_t> level_ptr, segments;
+};
+
 struct bmsp_matrix_s {
     // identity of this matrix's STRUCTURE: a fresh number at construction and after bmsp_matrix_invalidate(m, 1).  What one matrix remembers
     // about another (the row-merge hint below) is keyed by it -- not by a device pointer, which the pool hands out again
@@ -102,6 +113,8 @@ struct bmsp_matrix_s {
     // op N before its epilogue; both grow to the largest call seen and go with the views (drop_spmv_op_views)
     void *spmm_op_scratch = nullptr, *spmm_op_tmp = nullptr;
     int64_t spmm_op_scratch_elems = 0, spmm_op_tmp_elems = 0;
+    // bmsp_spsv: the plan per [op][fill], built by bmsp_spsv_analyse or the first solve; goes with the views (structure changes, free)
+    bmsp_spsv_plan_s spsv_plans[2][2];
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -269,6 +282,15 @@ bmsp_matrix_s *spgemm_masked_matrix(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_mat
 void spgemm_masked_values_into(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *M, double alpha, double beta, int flags, bmsp_matrix_s *out,
                                hipStream_t st);
 void spgemm_masked_launch_info(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *M, int out_transposed, bmsp_spgemm_masked_info *info);
+// spsv.hip: the triangular solve op(tri(A)) * x = alpha * b for either tile layout; its plan (levels, launch schedule) as a report; the
+// host part of the planner.  Both build the plan of (A, op, fill) if it is missing, which synchronises `st`.
+void spsv_check_args(int op, int fill, int diag);
+void spsv_check_matrix(const bmsp_matrix_s *A);
+void spsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *b, void *x, hipStream_t st);
+void spsv_analyse(bmsp_matrix_s *A, int op, int fill, int diag, hipStream_t st, bmsp_spsv_info *info);
+void spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
+               uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments);
+void drop_spsv_plans(bmsp_matrix_s *m);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

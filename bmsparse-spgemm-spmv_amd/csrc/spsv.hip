@@ -1,0 +1,447 @@
+// spsv.hip -- the sparse triangular solve op(tri(A)) * x = alpha * b (bmsp_spsv) for op in {N, T}, the lower or the upper triangle of a
+// square A in either tile layout and a unit or a stored diagonal, without a transpose, a conversion or a second copy of A.
+//
+// What is reused (spmv_op.hip): the tiles as 16-byte records in the order of the OUTPUT blocks with a pointer per output block and the
+// tile's other block index in every record -- the access pattern of a substitution -- and the lane mapping per (op, layout): MINOR = false,
+// the output index inside the block is the byte index of the bitmap; MINOR = true, it is the bit index inside each byte.  (N, row-major A)
+// has no view: it reads A's own arrays and the block-row pointer.
+//
+// What is new: the dependency schedule and the substitution inside the diagonal tile.
+//   plan     per (op, fill), structure only, cached on the handle: the level of an output block is 1 + the largest level of the blocks it
+//            depends on (every tile of the strict block triangle counts, whatever its bitmap), found in one pass on the host
+//            (spsv_plan) over the block pointer and the 4-byte other-index column; the blocks ordered by (level, index), the level
+//            pointer and the launch schedule.
+//   kernels  eight lanes per block-row, lane i owns row i of the block.  A group walks its block-row's records in chain order (ascending
+//            other index for a lower system, descending for an upper one) up to the diagonal tile, s = fma(-a_ij, x_j, s) per stored entry,
+//            then substitutes inside the diagonal tile in eight steps: the lane whose turn it is divides (the IEEE division sequence),
+//            x_c goes round the group by a wave shuffle, the lanes that store (i, c) take it into their sums.
+//            spsv_level_kernel: one launch per level, 32 block-rows per workgroup.
+//            spsv_chain_kernel: ONE workgroup walks a run of consecutive narrow levels, a workgroup barrier between two levels; x is
+//            stored and loaded again inside the workgroup, so x is never __restrict__ and never read through a read-only path.
+// Ordering comes from kernel boundaries and the workgroup barrier alone: no flag, no spin, no atomic, no cooperative launch.  Every x_i
+// has one writer and one fixed chain of operations: x is a pure function of A's arrays, b and alpha.
+#include "tile_pass.hip.h"
+#include <cstring>
+#include <vector>
+
+namespace bmsp {
+namespace {
+
+// Measured (tools/spsv_bench.py; DESIGN §4 "Triangular solve"): levels of at most this many block-rows are chained in one workgroup
+constexpr int64_t kChainDefault = 32;  // BMSP_SPSV_CHAIN
+constexpr int kGroups = kThreads / 8;  // block-rows per workgroup and pass
+
+// where the tile records come from: the view of (A, op), or (recs == null) A's own arrays
+struct SpsvTiles {
+    const uint4 *recs;
+    const uint64_t *keys, *bmps, *offsets;
+};
+
+// {bitmap lo, hi, value offset, the tile's other block index}
+__device__ __forceinline__ uint4 spsv_rec(const SpsvTiles &T, uint64_t t)
+{
+    if (T.recs) return T.recs[t];
+    const uint64_t b = T.bmps[t];
+    return make_uint4((uint32_t)b, (uint32_t)(b >> 32), (uint32_t)T.offsets[t], key_col(T.keys[t]));
+}
+
+__device__ __forceinline__ float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// Lane i of a group solves row i of output block I: every x the row depends on outside the block is final (an earlier launch, or an
+// earlier level of this workgroup behind a barrier).  b may be x (in place): a row's b is read by its own lane before that lane writes.
+template <typename S, bool MINOR, bool LOWER, bool UNIT>
+__device__ __forceinline__ void spsv_block_row(const SpsvTiles &T, const uint32_t *__restrict__ ptr, const S *__restrict__ vals,
+                                               typename TileValue<S>::R alpha, const typename TileValue<S>::R *b,
+                                               typename TileValue<S>::R *x, int64_t n, uint32_t I, int i)
+{
+#pragma clang fp contract(off)
+    using D = TileValue<S>;
+    using F = typename D::F;
+    const int64_t o = (int64_t)I * 8 + i;
+    const bool row = o < n;  // (the ragged last block: its rows beyond n store nothing and are not written)
+    F s = row ? alpha * b[o] : F(0);
+    int64_t t = LOWER ? (int64_t)ptr[I] : (int64_t)ptr[I + 1] - 1;
+    const int64_t end = LOWER ? (int64_t)ptr[I + 1] : (int64_t)ptr[I] - 1;
+    uint4 r = make_uint4(0u, 0u, 0u, 0u), next = r;
+    bool diag = false;
+    if (t != end) next = spsv_rec(T, (uint64_t)t);
+    for (; t != end; t += LOWER ? 1 : -1) {
+        r = next;
+        if (LOWER ? r.w >= I : r.w <= I) {  // the diagonal tile, or the first tile of the triangle that is not read
+            diag = r.w == I;
+            break;
+        }
+        // the next record of the block-row is on its way while this tile's values and x arrive (records do not depend on x)
+        const int64_t tn = t + (LOWER ? 1 : -1);
+        if (tn != end) next = spsv_rec(T, (uint64_t)tn);
+        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
+        const S *tv = vals + r.z;
+        const F *tx = x + (uint64_t)r.w * 8;  // only stored entries index it: never beyond the matrix
+        if (!MINOR) {
+            uint32_t byte = tile_byte(bmp, i);
+            if (LOWER) {
+                int k = tile_rank(bmp, 8 * i);
+                while (byte) {
+                    const int c = __builtin_clz(byte) - 24;
+                    byte &= ~(0x80u >> c);
+                    s = fused(-D::load(tv[k++]), tx[c], s);
+                }
+            } else {
+                int k = tile_rank(bmp, 8 * i) + __builtin_popcount(byte);
+                while (byte) {
+                    const int c = 7 - __builtin_ctz(byte);
+                    byte &= byte - 1;
+                    s = fused(-D::load(tv[--k]), tx[c], s);
+                }
+            }
+        } else {
+            uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
+            while (m) {
+                int p;
+                if (LOWER) p = tile_pop_first(m);
+                else { p = 63 - __builtin_ctzll(m); m &= m - 1; }
+                s = fused(-D::load(tv[tile_rank(bmp, p)]), tx[p >> 3], s);
+            }
+        }
+    }
+    F xi = s;  // no diagonal tile (unit diagonal): nothing inside the block
+    if (diag) {
+        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
+        const S *tv = vals + r.z;
+        F a[8], d = F(1);
+        uint32_t stored = 0;  // bit c: (i, c) lies in the strict triangle and is stored
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const int p = MINOR ? 8 * c + i : 8 * i + c;
+            a[c] = F(0);
+            if ((LOWER ? c < i : c > i) && tile_has(bmp, p)) {
+                a[c] = D::load(tv[tile_rank(bmp, p)]);
+                stored |= 1u << c;
+            }
+        }
+        if (!UNIT && tile_has(bmp, 9 * i)) d = D::load(tv[tile_rank(bmp, 9 * i)]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int c = LOWER ? k : 7 - k;
+            if (i == c) xi = UNIT ? s : s / d;
+            const F xc = __shfl(xi, c, 8);  // (the whole group is here: the walk above is the same for its eight lanes)
+            if ((stored >> c) & 1u) s = fused(-a[c], xc, s);
+        }
+    }
+    if (row) x[o] = xi;
+}
+
+// block-rows order[first .. first + width) of one level
+template <typename S, bool MINOR, bool LOWER, bool UNIT>
+__global__ __launch_bounds__(kThreads) void spsv_level_kernel(SpsvTiles T, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ order,
+                                                              uint32_t first, uint32_t width, const S *__restrict__ vals,
+                                                              typename TileValue<S>::R alpha, const typename TileValue<S>::R *b,
+                                                              typename TileValue<S>::R *x, int64_t n)
+{
+    const uint64_t g = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 3;
+    if (g >= width) return;  // (whole groups leave: a shuffle stays inside its group)
+    spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, n, order[first + g], (int)(threadIdx.x & 7));
+}
+
+// levels [l0, l1) by one workgroup; the level loop is uniform, the barrier orders the stores to x of a level before the loads of the next
+template <typename S, bool MINOR, bool LOWER, bool UNIT>
+__global__ __launch_bounds__(kThreads) void spsv_chain_kernel(SpsvTiles T, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ order,
+                                                              const uint32_t *__restrict__ level_ptr, uint32_t l0, uint32_t l1,
+                                                              const S *__restrict__ vals, typename TileValue<S>::R alpha,
+                                                              const typename TileValue<S>::R *b, typename TileValue<S>::R *x, int64_t n)
+{
+    const uint32_t g = threadIdx.x >> 3;
+    const int i = (int)(threadIdx.x & 7);
+    for (uint32_t l = l0; l < l1; l++) {
+        const uint64_t hi = level_ptr[l + 1];
+        for (uint64_t k = (uint64_t)level_ptr[l] + g; k < hi; k += kGroups)
+            spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, n, order[k], i);
+        __syncthreads();
+    }
+}
+
+// other[t] = the other block index of record t
+struct OtherColumn {
+    SpsvTiles T;
+    uint32_t *other;
+    __device__ void operator()(uint64_t t) const { other[t] = spsv_rec(T, t).w; }
+};
+
+// first[I] = the first row of output block I below n whose diagonal entry is not stored, ~0u if there is none
+struct MissingDiagonal {
+    SpsvTiles T;
+    const uint32_t *ptr;
+    int64_t n;
+    uint32_t *first;
+    __device__ void operator()(uint64_t I) const
+    {
+        uint32_t lo = ptr[I], hi = ptr[I + 1];
+        const uint32_t e = hi;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (spsv_rec(T, mid).w < (uint32_t)I) lo = mid + 1;
+            else hi = mid;
+        }
+        uint64_t bmp = 0;
+        if (lo < e) {
+            const uint4 r = spsv_rec(T, lo);
+            if (r.w == (uint32_t)I) bmp = (uint64_t)r.y << 32 | r.x;
+        }
+        uint32_t miss = ~0u;
+        for (int k = 7; k >= 0; k--)
+            if ((int64_t)I * 8 + k < n && !tile_has(bmp, 9 * k)) miss = (uint32_t)(I * 8 + k);
+        first[I] = miss;
+    }
+};
+
+int64_t chain_from_env()
+{
+    if (const char *e = getenv("BMSP_SPSV_CHAIN")) {
+        char *end = nullptr;
+        const long long c = strtoll(e, &end, 10);
+        if (end != e && c >= 0) return (int64_t)c;
+    }
+    return kChainDefault;
+}
+
+SpsvTiles tiles_of(const bmsp_matrix_s *A, const bmsp_spmv_op_view *w)
+{
+    if (w) return SpsvTiles{(const uint4 *)w->mem, nullptr, nullptr, nullptr};
+    return SpsvTiles{nullptr, A->keys, A->bmps, A->offsets};
+}
+
+// the view of (A, op), or null for (N, row-major A); *ptr = the pointer per output block
+const bmsp_spmv_op_view *view_of(bmsp_matrix_s *A, int op, hipStream_t st, const uint32_t **ptr)
+{
+    if (op == BMSP_OP_N && !A->transposed) {
+        ensure_rowptr(A, st);
+        *ptr = A->rowptr;
+        return nullptr;
+    }
+    const bmsp_spmv_op_view &w = spmv_op_ensure_view(A, op, st);
+    *ptr = op == BMSP_OP_T ? (const uint32_t *)((const char *)w.mem + w.off_ptr) : A->rowptr;
+    return &w;
+}
+
+bool effective_lower(int op, int fill) { return (fill == BMSP_FILL_LOWER) != (op == BMSP_OP_T); }
+
+// builds the plan of (A, op, fill) if it is missing: synchronises `st`
+bmsp_spsv_plan_s &ensure_plan(bmsp_matrix_s *A, int op, int fill, hipStream_t st)
+{
+    bmsp_spsv_plan_s &pl = A->spsv_plans[op][fill];
+    if (pl.mem) return pl;
+    const uint32_t *ptr = nullptr;
+    const bmsp_spmv_op_view *w = view_of(A, op, st, &ptr);
+    const SpsvTiles T = tiles_of(A, w);
+    const int64_t blocks = A->num_block_rows();
+    const uint64_t nb = (uint64_t)A->block_num;
+    DevBuf<uint32_t> d_other((size_t)nb), d_miss((size_t)blocks);
+    device_for_each(OtherColumn{T, d_other.p}, nb, st);
+    device_for_each(MissingDiagonal{T, ptr, (int64_t)A->num_rows, d_miss.p}, (uint64_t)blocks, st);
+    std::vector<uint32_t> hptr((size_t)blocks + 1, 0u), other((size_t)nb), miss((size_t)blocks);
+    BMSP_HIP(hipStreamSynchronize(st));
+    copy_d2h_staged(hptr.data(), ptr, 4 * ((size_t)blocks + 1));
+    if (nb) copy_d2h_staged(other.data(), d_other.p, 4 * (size_t)nb);
+    if (blocks) copy_d2h_staged(miss.data(), d_miss.p, 4 * (size_t)blocks);
+
+    bmsp_spsv_plan_s np;
+    np.blocks = blocks;
+    np.chain = chain_from_env();
+    for (int64_t I = 0; I < blocks && np.missing_diag_row < 0; I++)
+        if (miss[(size_t)I] != ~0u) np.missing_diag_row = (int64_t)miss[(size_t)I];
+    std::vector<uint32_t> order((size_t)blocks);
+    np.level_ptr.assign((size_t)blocks + 1, 0u);
+    np.segments.assign(3 * (size_t)blocks, 0u);
+    int64_t n_levels = 0, n_segments = 0;
+    spsv_plan(hptr.data(), other.data(), blocks, effective_lower(op, fill) ? 1 : 0, np.chain, nullptr, order.data(), np.level_ptr.data(),
+              np.segments.data(), &n_levels, &n_segments);
+    np.levels = n_levels;
+    np.level_ptr.resize((size_t)n_levels + 1);
+    np.segments.resize(3 * (size_t)n_segments);
+    for (int64_t l = 0; l < n_levels; l++) {
+        const int64_t wd = (int64_t)np.level_ptr[(size_t)l + 1] - (int64_t)np.level_ptr[(size_t)l];
+        if (wd > np.max_level_width) np.max_level_width = wd;
+    }
+    for (int64_t s = 0; s < n_segments; s++)
+        if (np.segments[3 * (size_t)s + 2]) {
+            np.chain_launches++;
+            np.chained_levels += (int64_t)np.segments[3 * (size_t)s + 1] - (int64_t)np.segments[3 * (size_t)s];
+        }
+    np.off_level_ptr = 4 * (size_t)blocks;
+    np.bytes = np.off_level_ptr + 4 * ((size_t)n_levels + 1);
+    DevBuf<char> mem(np.bytes);
+    if (blocks) copy_h2d_staged(mem.p, order.data(), 4 * (size_t)blocks);
+    copy_h2d_staged(mem.p + np.off_level_ptr, np.level_ptr.data(), 4 * ((size_t)n_levels + 1));
+    np.mem = (uint32_t *)mem.take();
+    pl = std::move(np);
+    return pl;
+}
+
+void refuse_missing_diagonal(const bmsp_spsv_plan_s &pl, int diag)
+{
+    if (diag == BMSP_DIAG_NON_UNIT && pl.missing_diag_row >= 0)
+        fail(BMSP_ERR_INVALID, "diag: BMSP_DIAG_NON_UNIT, but row %lld of A has no stored diagonal entry", (long long)pl.missing_diag_row);
+}
+
+template <typename S, bool MINOR, bool LOWER, bool UNIT>
+void launch_plan(const bmsp_matrix_s *A, const SpsvTiles &T, const uint32_t *ptr, const bmsp_spsv_plan_s &pl, double alpha, const void *b, void *x,
+                 hipStream_t st)
+{
+    using R = typename TileValue<S>::R;
+    const uint32_t *order = pl.mem, *level_ptr = (const uint32_t *)((const char *)pl.mem + pl.off_level_ptr);
+    for (size_t s = 0; s < pl.segments.size(); s += 3) {
+        const uint32_t l0 = pl.segments[s], l1 = pl.segments[s + 1];
+        if (pl.segments[s + 2]) {
+            hipLaunchKernelGGL((spsv_chain_kernel<S, MINOR, LOWER, UNIT>), dim3(1), dim3(kThreads), 0, st, T, ptr, order, level_ptr, l0, l1,
+                               (const S *)A->values, (R)alpha, (const R *)b, (R *)x, (int64_t)A->num_rows);
+        } else {
+            const uint32_t first = pl.level_ptr[l0], width = pl.level_ptr[l0 + 1] - first;
+            hipLaunchKernelGGL((spsv_level_kernel<S, MINOR, LOWER, UNIT>), grid_for((uint64_t)width * 8), dim3(kThreads), 0, st, T, ptr, order,
+                               first, width, (const S *)A->values, (R)alpha, (const R *)b, (R *)x, (int64_t)A->num_rows);
+        }
+        BMSP_CHECK_LAUNCH();
+    }
+}
+
+template <typename S, bool MINOR, bool LOWER, typename... Args>
+void launch_diag(bool unit, Args &&...args)
+{
+    if (unit) launch_plan<S, MINOR, LOWER, true>(args...);
+    else launch_plan<S, MINOR, LOWER, false>(args...);
+}
+
+template <typename S, typename... Args>
+void launch_variant(bool minor, bool lower, bool unit, Args &&...args)
+{
+    if (minor) {
+        if (lower) launch_diag<S, true, true>(unit, args...);
+        else launch_diag<S, true, false>(unit, args...);
+    } else {
+        if (lower) launch_diag<S, false, true>(unit, args...);
+        else launch_diag<S, false, false>(unit, args...);
+    }
+}
+
+}  // namespace
+
+void spsv_check_args(int op, int fill, int diag)
+{
+    spmv_op_check_op(op);
+    if (fill != BMSP_FILL_LOWER && fill != BMSP_FILL_UPPER)
+        fail(BMSP_ERR_INVALID, "fill must be BMSP_FILL_LOWER (0) or BMSP_FILL_UPPER (1) (got %d)", fill);
+    if (diag != BMSP_DIAG_NON_UNIT && diag != BMSP_DIAG_UNIT)
+        fail(BMSP_ERR_INVALID, "diag must be BMSP_DIAG_NON_UNIT (0) or BMSP_DIAG_UNIT (1) (got %d)", diag);
+}
+
+void spsv_check_matrix(const bmsp_matrix_s *A)
+{
+    if (A->num_rows != A->num_cols) fail(BMSP_ERR_INVALID, "spsv: matrix A must be square (it is %d x %d)", A->num_rows, A->num_cols);
+    spmv_op_check_matrix(A, "spsv");
+}
+
+void drop_spsv_plans(bmsp_matrix_s *m)
+{
+    for (auto &per_op : m->spsv_plans)
+        for (bmsp_spsv_plan_s &pl : per_op) {
+            pool_free(pl.mem);
+            pl = bmsp_spsv_plan_s();
+        }
+}
+
+// Levels and launch schedule of a substitution over `blocks` output blocks whose records [ptr[I], ptr[I + 1]) carry the other block
+// index other[t]: block I depends on every other[t] < I (lower) or > I (upper).  Host only.
+void spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
+               uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
+{
+    if (blocks < 0) fail(BMSP_ERR_INVALID, "blocks must be >= 0 (got %lld)", (long long)blocks);
+    if (chain < 0) fail(BMSP_ERR_INVALID, "chain must be >= 0 (got %lld)", (long long)chain);
+    if (blocks && !ptr) fail(BMSP_ERR_INVALID, "ptr is null");
+    if (blocks >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "spsv: 2^32 blocks or more");
+    for (int64_t I = 0; I < blocks; I++)
+        if (ptr[I + 1] < ptr[I]) fail(BMSP_ERR_INVALID, "ptr decreases at block %lld", (long long)I);
+    if (blocks && ptr[blocks] > ptr[0] && !other) fail(BMSP_ERR_INVALID, "other is null");
+    for (uint64_t t = blocks ? ptr[0] : 0; blocks && t < ptr[blocks]; t++)
+        if ((int64_t)other[t] >= blocks) fail(BMSP_ERR_INVALID, "other[%llu] = %u is not below blocks (%lld)", (unsigned long long)t, other[t], (long long)blocks);
+    std::vector<uint32_t> lev((size_t)blocks, 0u);
+    int64_t levels = 0;
+    for (int64_t k = 0; k < blocks; k++) {
+        const int64_t I = lower ? k : blocks - 1 - k;
+        uint32_t l = 0;
+        for (uint64_t t = ptr[I]; t < ptr[I + 1]; t++) {
+            const int64_t J = other[t];
+            if ((lower ? J < I : J > I) && lev[(size_t)J] + 1 > l) l = lev[(size_t)J] + 1;
+        }
+        lev[(size_t)I] = l;
+        if ((int64_t)l + 1 > levels) levels = (int64_t)l + 1;
+    }
+    std::vector<uint32_t> lp((size_t)levels + 1, 0u);
+    for (int64_t I = 0; I < blocks; I++) lp[(size_t)lev[(size_t)I] + 1]++;
+    for (int64_t l = 0; l < levels; l++) lp[(size_t)l + 1] += lp[(size_t)l];
+    if (order) {
+        std::vector<uint32_t> at(lp.begin(), lp.end() - 1);
+        for (int64_t I = 0; I < blocks; I++) order[at[lev[(size_t)I]]++] = (uint32_t)I;
+    }
+    if (level_of) memcpy(level_of, lev.data(), 4 * (size_t)blocks);
+    if (level_ptr) memcpy(level_ptr, lp.data(), 4 * ((size_t)levels + 1));
+    // a maximal run of at least two consecutive levels of at most `chain` block-rows each is one chain launch; every other level its own
+    int64_t ns = 0;
+    const auto emit = [&](int64_t l0, int64_t l1, uint32_t kind) {
+        if (segments) { uint32_t *s = segments + 3 * ns; s[0] = (uint32_t)l0; s[1] = (uint32_t)l1; s[2] = kind; }
+        ns++;
+    };
+    for (int64_t l = 0; l < levels;) {
+        int64_t e = l;
+        while (e < levels && (int64_t)(lp[(size_t)e + 1] - lp[(size_t)e]) <= chain) e++;
+        if (e - l >= 2) { emit(l, e, 1u); l = e; continue; }
+        emit(l, l + 1, 0u);
+        l++;
+    }
+    if (n_levels) *n_levels = levels;
+    if (n_segments) *n_segments = ns;
+}
+
+void spsv_analyse(bmsp_matrix_s *A, int op, int fill, int diag, hipStream_t st, bmsp_spsv_info *info)
+{
+    spsv_check_args(op, fill, diag);
+    spsv_check_matrix(A);
+    const bmsp_spsv_plan_s &pl = ensure_plan(A, op, fill, st);
+    refuse_missing_diagonal(pl, diag);
+    if (!info) return;
+    memset(info, 0, sizeof *info);
+    info->levels = pl.levels;
+    info->max_level_width = pl.max_level_width;
+    info->launches = (int64_t)(pl.segments.size() / 3);
+    info->chain_launches = pl.chain_launches;
+    info->chained_levels = pl.chained_levels;
+    info->plan_bytes = (int64_t)pl.bytes;
+    if (pl.blocks == 0) {
+        snprintf(info->kernel, sizeof info->kernel, "none (empty matrix)");
+        return;
+    }
+    const bool minor = (op == BMSP_OP_T) != (A->transposed != 0);
+    snprintf(info->kernel, sizeof info->kernel, "spsv_level_kernel<%s, %s, %s, %s>",
+             A->dtype == BMSP_F16 ? "F16" : (A->dtype == BMSP_F32 ? "F32" : "F64"), minor ? "MINOR" : "MAJOR",
+             effective_lower(op, fill) ? "LOWER" : "UPPER", diag == BMSP_DIAG_UNIT ? "UNIT" : "NON_UNIT");
+}
+
+void spsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *b, void *x, hipStream_t st)
+{
+    spsv_check_args(op, fill, diag);
+    spsv_check_matrix(A);
+    const bmsp_spsv_plan_s &pl = ensure_plan(A, op, fill, st);
+    refuse_missing_diagonal(pl, diag);
+    if (pl.blocks == 0) return;
+    const uint32_t *ptr = nullptr;
+    const bmsp_spmv_op_view *w = view_of(A, op, st, &ptr);  // (both exist: the plan was made from them)
+    const SpsvTiles T = tiles_of(A, w);
+    const bool minor = (op == BMSP_OP_T) != (A->transposed != 0);
+    dispatch_dtype(A->dtype, [&](auto s) {
+        using S = decltype(s);
+        launch_variant<S>(minor, effective_lower(op, fill), diag == BMSP_DIAG_UNIT, A, T, ptr, pl, alpha, b, x, st);
+    });
+}
+
+}  // namespace bmsp
+
+BMSP_DEFINE_WARM(spsv)

@@ -25,7 +25,10 @@ SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
 OP_N, OP_T = 0, 1
 SDDMM_MUL_S = 1
 MASKED_MUL_M = 1
+FILL_LOWER, FILL_UPPER = 0, 1
+DIAG_NON_UNIT, DIAG_UNIT = 0, 1
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
+_FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
 
 # every symbol include/bmsp.h declares (checked by tests/test_abi.py against the header text)
@@ -38,7 +41,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -103,6 +106,15 @@ class SpgemmMaskedInfo(C.Structure):
 
     def as_dict(self):
         return {"kernel": self.kernel.decode(), "lanes": self.lanes, "pairs": self.pairs, "view_bytes": self.view_bytes}
+
+
+class SpsvInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("levels", C.c_int64), ("max_level_width", C.c_int64), ("launches", C.c_int64),
+                ("chain_launches", C.c_int64), ("chained_levels", C.c_int64), ("plan_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {"kernel": self.kernel.decode(), "levels": self.levels, "max_level_width": self.max_level_width, "launches": self.launches,
+                "chain_launches": self.chain_launches, "chained_levels": self.chained_levels, "plan_bytes": self.plan_bytes}
 
 
 class ShardStats(C.Structure):
@@ -177,6 +189,9 @@ def lib():
         L.bmsp_spmv_op.argtypes = [vp, i, C.c_double, vp, C.c_double, vp, vp]
         L.bmsp_spmv_op_launch_info.argtypes = [vp, i, p(SpmvOpInfo)]
         L.bmsp_spmv_op_plan_items.argtypes = [vp, i64, i64, vp, vp, p(i64), p(i64), p(i64)]
+        L.bmsp_spsv_analyse.argtypes = [vp, i, i, i, vp, p(SpsvInfo)]
+        L.bmsp_spsv.argtypes = [vp, i, i, i, C.c_double, vp, vp, vp]
+        L.bmsp_spsv_plan.argtypes = [vp, vp, i64, i, i64, vp, vp, vp, vp, p(i64), p(i64)]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -484,6 +499,10 @@ class BmSpMatrix:
         """the same into this matrix's own values (bmsp_sddmm_values with out == S)"""
         return sddmm_values(self, self, X, Y, k, alpha, beta, mul_s, ldx, ldy, stream)
 
+    def solve_triangular(self, b, op="N", fill="lower", unit_diag=False, alpha=1.0, x=None, stream=None):
+        """x with op(tri(this)) * x = alpha * b: pybmsp.spsv"""
+        return spsv(self, b, op, fill, unit_diag, alpha, x, stream)
+
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
         return spgemm_masked(self, B, M, alpha, beta, mul_m, transposed, stream)
@@ -713,6 +732,54 @@ def spmv_op_plan_items(ptr, split):
     check(lib().bmsp_spmv_op_plan_items(pt.ctypes.data, blocks, int(split), items.ctypes.data, folds.ctypes.data, C.byref(ni), C.byref(nf),
                                         C.byref(ns)))
     return items, folds, ns.value
+
+
+def _fill(fill):
+    if fill not in _FILLS:
+        raise ValueError("fill must be 'lower' or 'upper' (got %r)" % (fill,))
+    return _FILLS[fill]
+
+
+def spsv(A, b, op="N", fill="lower", unit_diag=False, alpha=1.0, x=None, stream=None):
+    """Solves op(tri(A)) * x = alpha * b on the device (bmsp_spsv): tri(A) the "lower" / "upper" triangle of the square A (named before
+    op), op "N" or "T", A in either tile layout; unit_diag takes the diagonal as 1 and never reads the stored one.  b: DeviceArray of
+    num_rows entries (float32, float64 for F64); x: the same, made when None, and may be b itself (in place).  Returns x.  One fused
+    multiply-add per stored entry in the order of a sequential substitution, one IEEE division per row: the bits are fixed.  Asynchronous
+    on `stream` once the plan of (A, op, fill) exists (spsv_analyse, or the first call)."""
+    o, f = _op(op), _fill(fill)
+    i = A.info()
+    vt = np.dtype(OUT_DTYPE[i["dtype"]])
+    if b.dtype != vt or b.n < i["num_rows"]:
+        raise ValueError("b must hold %d entries of %s" % (i["num_rows"], vt.name))
+    if x is None:
+        x = DeviceArray(i["num_rows"], vt)
+    elif x.dtype != vt or x.n < i["num_rows"]:
+        raise ValueError("x must hold %d entries of %s" % (i["num_rows"], vt.name))
+    check(lib().bmsp_spsv(A.h, o, f, DIAG_UNIT if unit_diag else DIAG_NON_UNIT, float(alpha), b.ptr, x.ptr, stream))
+    return x
+
+
+def spsv_analyse(A, op, fill, unit_diag=False, stream=None):
+    """{"kernel", "levels", "max_level_width", "launches", "chain_launches", "chained_levels", "plan_bytes"} of the plan spsv(A, ., op,
+    fill) runs; builds the plan if it is missing, which synchronises `stream` (bmsp_spsv_analyse)."""
+    info = SpsvInfo()
+    check(lib().bmsp_spsv_analyse(A.h, _op(op), _fill(fill), DIAG_UNIT if unit_diag else DIAG_NON_UNIT, stream, C.byref(info)))
+    return info.as_dict()
+
+
+def spsv_plan(ptr, other, lower, chain):
+    """(level_of [blocks], order [blocks], level_ptr [levels + 1], segments [launches, 3]) of the solve's planner for a block pointer and
+    the other-index column of its records (host arithmetic of spsv.hip; bmsp_spsv_plan)."""
+    pt = np.ascontiguousarray(ptr, dtype=np.uint32)
+    ot = np.ascontiguousarray(other, dtype=np.uint32)
+    blocks = max(0, pt.size - 1)
+    level_of, order = np.zeros(blocks, np.uint32), np.zeros(blocks, np.uint32)
+    level_ptr, segments = np.zeros(blocks + 1, np.uint32), np.zeros((blocks, 3), np.uint32)
+    nl, ns = C.c_int64(), C.c_int64()
+    check(lib().bmsp_spsv_plan(pt.ctypes.data if pt.size else None, ot.ctypes.data if ot.size else None, blocks, int(bool(lower)), int(chain),
+                               level_of.ctypes.data, order.ctypes.data, level_ptr.ctypes.data, segments.ctypes.data, C.byref(nl),
+                               C.byref(ns)))
+    return level_of, order, level_ptr[:nl.value + 1].copy(), segments[:ns.value].copy()
 
 
 def spmv_chunk_layout(A):

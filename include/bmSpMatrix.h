@@ -299,6 +299,23 @@ inline void bmSparse_SpMV_op(bmSpMatrix<ValueIn> &A, int op, double alpha, const
     bmsp::check(bmsp_synchronize());
 }
 
+/* Triangular solve (bmsp_spsv): op(tri(A)) * x = alpha * b, tri(A) the BMSP_FILL_LOWER / BMSP_FILL_UPPER triangle of the square A (named
+ * before op), diag = BMSP_DIAG_NON_UNIT / BMSP_DIAG_UNIT, A in either tile layout.  b and x are device pointers to num_rows entries (float,
+ * double for double) and may be the same; synchronous like bmSparse_SpMV.  bmSparse_SpSV_analyse builds the cached plan of (A, op, fill)
+ * ahead of the first solve and reports it (info may be null). */
+template <class ValueIn>
+inline void bmSparse_SpSV(bmSpMatrix<ValueIn> &A, int op, int fill, int diag, double alpha, const typename bmsp::vector_of<ValueIn>::type *b,
+                          typename bmsp::vector_of<ValueIn>::type *x)
+{
+    bmsp::check(bmsp_spsv(A.handle(), op, fill, diag, alpha, b, x, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+template <class ValueIn>
+inline void bmSparse_SpSV_analyse(bmSpMatrix<ValueIn> &A, int op, int fill, int diag, bmsp_spsv_info *info = nullptr)
+{
+    bmsp::check(bmsp_spsv_analyse(A.handle(), op, fill, diag, nullptr, info));
+}
+
 /* Multi-vector form: U = A * V for k vectors, V row-major num_cols x k, U row-major num_rows x k. */
 template <class ValueIn, class ValueOut> inline void bmSparse_SpMM(bmSpMatrix<ValueIn> &A, ValueIn *V, ValueOut *U, int k)
 {

@@ -354,6 +354,62 @@ int bmsp_spmv_op_launch_info(bmsp_matrix_t A, int op, bmsp_spmv_op_info *info);
 int bmsp_spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
                             int64_t *split_blocks, int64_t *slots);
 
+/* SpSV, the sparse triangular solve on the device: op(tri(A)) * x = alpha * b, tri(A) the lower or the upper triangle of a square A in
+ * EITHER tile layout, op(.) = BMSP_OP_N / BMSP_OP_T, the diagonal stored or taken as 1 -- a Gauss-Seidel sweep, the application of an
+ * incomplete factor, the substitution after a factorisation, without bmsp_matrix_to_csr_device and another library.  No conversion, no
+ * transpose, no second copy of A.  Nothing in the reference is replaced (it has no solve).
+ *   Operands: A is n x n, F32, F16 or F64.  b and x hold n entries of the vector type (float for F32 / F16, double for F64: the convention
+ *       of bmsp_matrix_diagonal and _scale).  d_x == d_b (in place) is legal; any other overlap is the caller's error.  `fill` names the
+ *       triangle of A that is read, BEFORE op: the effective system is lower iff (fill == BMSP_FILL_LOWER) != (op == BMSP_OP_T).  Tiles on
+ *       the other side of the block diagonal are never read, nor the other-side entries of a diagonal tile, nor -- under BMSP_DIAG_UNIT --
+ *       the stored diagonal: a NaN stored there does not reach x.  A's four arrays are not modified.
+ *   Numerics, fixed bit for bit: alpha is rounded once to the vector type and s = fl(alpha * b_i); then one fused multiply-add per STORED
+ *       entry of row i of the effective strict triangle, s = fma(-a_ij, x_j, s), in the order a sequential substitution meets them
+ *       (ascending j for a lower system, descending j for an upper one); then x_i = s / a_ii as one IEEE division (the full division
+ *       sequence, never a reciprocal), or x_i = s under BMSP_DIAG_UNIT.  fp32 arithmetic (double for F64), F16 values widened exactly,
+ *       subnormals kept.  A stored zero on the diagonal gives what IEEE gives; Inf / NaN propagate along dependencies only.  x is a pure
+ *       function of A's arrays, b and alpha: it does not depend on scheduling, on BMSP_SPSV_CHAIN or on the stream.  Every x_i, i < n, is
+ *       written (rows of block-rows without tiles too, under BMSP_DIAG_UNIT); nothing at or beyond n is.
+ *   Plan: cached on the handle per (op, fill), structure only.  The level of a block-row (of op(A)) is 1 + the largest level of the
+ *       block-rows it depends on, every tile of the strict block triangle counting as a dependency whatever its bitmap; the plan holds the
+ *       block-rows ordered by (level, index), the level pointer and the launch schedule.  It is built by bmsp_spsv_analyse or by the first
+ *       bmsp_spsv that finds none: the build copies the block pointer and the 4-byte other-index column to the host, levels them there in
+ *       one pass (bmsp_spsv_plan), uploads the result and synchronises `stream`.  Op T and column-major matrices reuse the cached view of
+ *       bmsp_spmv_op (built if missing); (N, row-major A) reads A's own arrays.  Values are read from A at every call: a value-only update
+ *       needs no bmsp_matrix_invalidate.  bmsp_matrix_invalidate(A, 1) and bmsp_matrix_free drop the plan; bmsp_matrix_invalidate(A, 0),
+ *       bmsp_matrix_copy_values, _scale_values and _add_values into A keep it.  Once the plan exists bmsp_spsv is asynchronous on
+ *       `stream`: launches only, no temporary, nothing read back; solves of one handle may run on different streams.
+ *   Kernels (vector ALU): eight lanes per block-row, a lane per row.  spsv_level_kernel: one launch per level, 32 block-rows per
+ *       workgroup.  spsv_chain_kernel: ONE workgroup walks a maximal run of at least two consecutive levels of at most CHAIN block-rows
+ *       each, a workgroup barrier between levels.  There is no waiting between workgroups anywhere: no flag, no spin, no atomic, no
+ *       cooperative launch.  BMSP_SPSV_CHAIN=<block-rows> is read when a plan is built; 0 = never chain, one launch per level (default 32,
+ *       one pass of a workgroup: see README).  A block-row of thousands of tiles is one lane group's serial chain, and a matrix of
+ *       thousands of levels is thousands of dependent steps: the fixed order is kept, long block-rows are not split.
+ *   bmsp_spsv_analyse: builds the plan if it is missing and reports it (info may be NULL): the level kernel's instantiation by name
+ *       ("spsv_level_kernel<F32, MAJOR, LOWER, NON_UNIT>": dtype; MAJOR / MINOR as for bmsp_spmv_op; the EFFECTIVE triangle; the diagonal;
+ *       "none (empty matrix)" for n = 0), the levels, the widest level in block-rows, the launches of one solve, how many of them are chain
+ *       launches and how many levels those cover, and the device bytes of the plan.
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles: op, fill or diag not 0 / 1; null A, d_b, d_x;
+ *   num_rows != num_cols; row-panel views; BMSP_DIAG_NON_UNIT with a row i < n whose (i, i) is not stored (found during the analysis; the
+ *   message names the first such row; a BMSP_DIAG_UNIT call of the same handle still works).  BMSP_ERR_LIMIT: 2^32 tiles or values or more. */
+#define BMSP_FILL_LOWER 0
+#define BMSP_FILL_UPPER 1
+#define BMSP_DIAG_NON_UNIT 0
+#define BMSP_DIAG_UNIT 1
+typedef struct { char kernel[64]; int64_t levels, max_level_width, launches, chain_launches, chained_levels, plan_bytes; } bmsp_spsv_info;
+int bmsp_spsv_analyse(bmsp_matrix_t A, int op, int fill, int diag, void *stream, bmsp_spsv_info *info /* may be NULL */);
+int bmsp_spsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_b, void *d_x, void *stream);
+/* The planner, host only, no GPU call: over `blocks` output blocks whose records [ptr[I], ptr[I + 1]) carry the other block index
+ * other[t], block I depends on every other[t] < I (lower != 0) or > I (lower == 0).  level_of[I] (blocks entries) = 0 without
+ * dependencies, else 1 + the largest level depended on; order (blocks entries) = the blocks sorted by (level, index); level_ptr
+ * (*n_levels + 1 entries; at most blocks + 1) = where each level begins in order; segments (3 words per launch; at most 3 * blocks) =
+ * {first level, end level, kind}: kind 1 = one chain launch over a maximal run of at least two consecutive levels of at most `chain`
+ * blocks each, kind 0 = one level launch.  Every output pointer may be NULL.  Refused with BMSP_ERR_INVALID: negative blocks or chain, null
+ * ptr while blocks > 0, a ptr that decreases, an `other` index >= blocks. */
+int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain,
+                   uint32_t *level_of, uint32_t *order, uint32_t *level_ptr, uint32_t *segments,
+                   int64_t *n_levels, int64_t *n_segments);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
