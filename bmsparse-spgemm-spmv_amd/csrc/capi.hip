@@ -742,6 +742,29 @@ int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, i
     BMSP_API_END
 }
 
+int bmsp_spsm(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_B, int64_t ldb, void *d_X, int64_t ldx, int k, void *stream)
+{
+    BMSP_API_BEGIN
+    spsm_check_args(op, fill, diag, k, ldb, ldx);
+    need(A, "matrix A"); need(d_B, "d_B"); need(d_X, "d_X");
+    spsv_check_matrix(A);
+    spsm_check_in_place(d_B, ldb, d_X, ldx);
+    load_kernels();
+    spsm(A, op, fill, diag, alpha, d_B, ldb, d_X, ldx, k, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_spsm_launch_info(bmsp_matrix_t A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, void *stream, bmsp_spsm_info *info)
+{
+    BMSP_API_BEGIN
+    spsm_check_args(op, fill, diag, k, ldb, ldx);
+    need(A, "matrix A"); need(info, "info");
+    spsv_check_matrix(A);
+    load_kernels();
+    spsm_launch_info(A, op, fill, diag, k, ldb, ldx, as_stream(stream), info);
+    BMSP_API_END
+}
+
 int bmsp_comm_unique_id(void *id_bytes)
 {
     BMSP_API_BEGIN

@@ -291,6 +291,12 @@ void spsv_analyse(bmsp_matrix_s *A, int op, int fill, int diag, hipStream_t st, 
 void spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments);
 void drop_spsv_plans(bmsp_matrix_s *m);
+// spsm.hip: the triangular solve for k right-hand sides, op(tri(A)) * X = alpha * B, on the plan of spsv.hip (built if it is missing,
+// which synchronises `st`); what that call launches
+void spsm_check_args(int op, int fill, int diag, int k, int64_t ldb, int64_t ldx);
+void spsm_check_in_place(const void *B, int64_t ldb, const void *X, int64_t ldx);
+void spsm(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *B, int64_t ldb, void *X, int64_t ldx, int k, hipStream_t st);
+void spsm_launch_info(bmsp_matrix_s *A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, hipStream_t st, bmsp_spsm_info *info);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -1,0 +1,157 @@
+// spsv_plan.hip.h -- what the triangular solves share (spsv.hip: one right-hand side; spsm.hip: k of them): where the tile records of
+// (A, op) come from and how one is read, the fused multiply-add of the substitution, and the cached plan of (A, op, fill) -- its build
+// and the refusal it carries.  The kernels stay in their files: they differ in what a lane owns (a row there, a column of X here).
+#ifndef BMSP_SPSV_PLAN_HIP_H_
+#define BMSP_SPSV_PLAN_HIP_H_
+
+#include "tile_pass.hip.h"
+#include <cstring>
+#include <vector>
+
+namespace bmsp {
+
+// Measured (tools/spsv_bench.py; DESIGN §4 "Triangular solve"): levels of at most this many block-rows are chained in one workgroup
+constexpr int64_t kChainDefault = 32;  // BMSP_SPSV_CHAIN
+
+// where the tile records come from: the view of (A, op), or (recs == null) A's own arrays
+struct SpsvTiles {
+    const uint4 *recs;
+    const uint64_t *keys, *bmps, *offsets;
+};
+
+// {bitmap lo, hi, value offset, the tile's other block index}
+__device__ __forceinline__ uint4 spsv_rec(const SpsvTiles &T, uint64_t t)
+{
+    if (T.recs) return T.recs[t];
+    const uint64_t b = T.bmps[t];
+    return make_uint4((uint32_t)b, (uint32_t)(b >> 32), (uint32_t)T.offsets[t], key_col(T.keys[t]));
+}
+
+__device__ __forceinline__ float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// other[t] = the other block index of record t
+struct OtherColumn {
+    SpsvTiles T;
+    uint32_t *other;
+    __device__ void operator()(uint64_t t) const { other[t] = spsv_rec(T, t).w; }
+};
+
+// first[I] = the first row of output block I below n whose diagonal entry is not stored, ~0u if there is none
+struct MissingDiagonal {
+    SpsvTiles T;
+    const uint32_t *ptr;
+    int64_t n;
+    uint32_t *first;
+    __device__ void operator()(uint64_t I) const
+    {
+        uint32_t lo = ptr[I], hi = ptr[I + 1];
+        const uint32_t e = hi;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (spsv_rec(T, mid).w < (uint32_t)I) lo = mid + 1;
+            else hi = mid;
+        }
+        uint64_t bmp = 0;
+        if (lo < e) {
+            const uint4 r = spsv_rec(T, lo);
+            if (r.w == (uint32_t)I) bmp = (uint64_t)r.y << 32 | r.x;
+        }
+        uint32_t miss = ~0u;
+        for (int k = 7; k >= 0; k--)
+            if ((int64_t)I * 8 + k < n && !tile_has(bmp, 9 * k)) miss = (uint32_t)(I * 8 + k);
+        first[I] = miss;
+    }
+};
+
+inline int64_t chain_from_env()
+{
+    if (const char *e = getenv("BMSP_SPSV_CHAIN")) {
+        char *end = nullptr;
+        const long long c = strtoll(e, &end, 10);
+        if (end != e && c >= 0) return (int64_t)c;
+    }
+    return kChainDefault;
+}
+
+inline SpsvTiles tiles_of(const bmsp_matrix_s *A, const bmsp_spmv_op_view *w)
+{
+    if (w) return SpsvTiles{(const uint4 *)w->mem, nullptr, nullptr, nullptr};
+    return SpsvTiles{nullptr, A->keys, A->bmps, A->offsets};
+}
+
+// the view of (A, op), or null for (N, row-major A); *ptr = the pointer per output block
+inline const bmsp_spmv_op_view *view_of(bmsp_matrix_s *A, int op, hipStream_t st, const uint32_t **ptr)
+{
+    if (op == BMSP_OP_N && !A->transposed) {
+        ensure_rowptr(A, st);
+        *ptr = A->rowptr;
+        return nullptr;
+    }
+    const bmsp_spmv_op_view &w = spmv_op_ensure_view(A, op, st);
+    *ptr = op == BMSP_OP_T ? (const uint32_t *)((const char *)w.mem + w.off_ptr) : A->rowptr;
+    return &w;
+}
+
+inline bool effective_lower(int op, int fill) { return (fill == BMSP_FILL_LOWER) != (op == BMSP_OP_T); }
+
+// builds the plan of (A, op, fill) if it is missing: synchronises `st`
+inline bmsp_spsv_plan_s &ensure_plan(bmsp_matrix_s *A, int op, int fill, hipStream_t st)
+{
+    bmsp_spsv_plan_s &pl = A->spsv_plans[op][fill];
+    if (pl.mem) return pl;
+    const uint32_t *ptr = nullptr;
+    const bmsp_spmv_op_view *w = view_of(A, op, st, &ptr);
+    const SpsvTiles T = tiles_of(A, w);
+    const int64_t blocks = A->num_block_rows();
+    const uint64_t nb = (uint64_t)A->block_num;
+    DevBuf<uint32_t> d_other((size_t)nb), d_miss((size_t)blocks);
+    device_for_each(OtherColumn{T, d_other.p}, nb, st);
+    device_for_each(MissingDiagonal{T, ptr, (int64_t)A->num_rows, d_miss.p}, (uint64_t)blocks, st);
+    std::vector<uint32_t> hptr((size_t)blocks + 1, 0u), other((size_t)nb), miss((size_t)blocks);
+    BMSP_HIP(hipStreamSynchronize(st));
+    copy_d2h_staged(hptr.data(), ptr, 4 * ((size_t)blocks + 1));
+    if (nb) copy_d2h_staged(other.data(), d_other.p, 4 * (size_t)nb);
+    if (blocks) copy_d2h_staged(miss.data(), d_miss.p, 4 * (size_t)blocks);
+
+    bmsp_spsv_plan_s np;
+    np.blocks = blocks;
+    np.chain = chain_from_env();
+    for (int64_t I = 0; I < blocks && np.missing_diag_row < 0; I++)
+        if (miss[(size_t)I] != ~0u) np.missing_diag_row = (int64_t)miss[(size_t)I];
+    std::vector<uint32_t> order((size_t)blocks);
+    np.level_ptr.assign((size_t)blocks + 1, 0u);
+    np.segments.assign(3 * (size_t)blocks, 0u);
+    int64_t n_levels = 0, n_segments = 0;
+    spsv_plan(hptr.data(), other.data(), blocks, effective_lower(op, fill) ? 1 : 0, np.chain, nullptr, order.data(), np.level_ptr.data(),
+              np.segments.data(), &n_levels, &n_segments);
+    np.levels = n_levels;
+    np.level_ptr.resize((size_t)n_levels + 1);
+    np.segments.resize(3 * (size_t)n_segments);
+    for (int64_t l = 0; l < n_levels; l++) {
+        const int64_t wd = (int64_t)np.level_ptr[(size_t)l + 1] - (int64_t)np.level_ptr[(size_t)l];
+        if (wd > np.max_level_width) np.max_level_width = wd;
+    }
+    for (int64_t s = 0; s < n_segments; s++)
+        if (np.segments[3 * (size_t)s + 2]) {
+            np.chain_launches++;
+            np.chained_levels += (int64_t)np.segments[3 * (size_t)s + 1] - (int64_t)np.segments[3 * (size_t)s];
+        }
+    np.off_level_ptr = 4 * (size_t)blocks;
+    np.bytes = np.off_level_ptr + 4 * ((size_t)n_levels + 1);
+    DevBuf<char> mem(np.bytes);
+    if (blocks) copy_h2d_staged(mem.p, order.data(), 4 * (size_t)blocks);
+    copy_h2d_staged(mem.p + np.off_level_ptr, np.level_ptr.data(), 4 * ((size_t)n_levels + 1));
+    np.mem = (uint32_t *)mem.take();
+    pl = std::move(np);
+    return pl;
+}
+
+inline void refuse_missing_diagonal(const bmsp_spsv_plan_s &pl, int diag)
+{
+    if (diag == BMSP_DIAG_NON_UNIT && pl.missing_diag_row >= 0)
+        fail(BMSP_ERR_INVALID, "diag: BMSP_DIAG_NON_UNIT, but row %lld of A has no stored diagonal entry", (long long)pl.missing_diag_row);
+}
+
+}  // namespace bmsp
+#endif

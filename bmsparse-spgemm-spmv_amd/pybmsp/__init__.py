@@ -41,7 +41,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -115,6 +115,16 @@ class SpsvInfo(C.Structure):
     def as_dict(self):
         return {"kernel": self.kernel.decode(), "levels": self.levels, "max_level_width": self.max_level_width, "launches": self.launches,
                 "chain_launches": self.chain_launches, "chained_levels": self.chained_levels, "plan_bytes": self.plan_bytes}
+
+
+class SpsmInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("col_chunks", C.c_int), ("levels", C.c_int64), ("launches", C.c_int64),
+                ("chain_launches", C.c_int64), ("chained_levels", C.c_int64), ("plan_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
 
 
 class ShardStats(C.Structure):
@@ -192,6 +202,8 @@ def lib():
         L.bmsp_spsv_analyse.argtypes = [vp, i, i, i, vp, p(SpsvInfo)]
         L.bmsp_spsv.argtypes = [vp, i, i, i, C.c_double, vp, vp, vp]
         L.bmsp_spsv_plan.argtypes = [vp, vp, i64, i, i64, vp, vp, vp, vp, p(i64), p(i64)]
+        L.bmsp_spsm.argtypes = [vp, i, i, i, C.c_double, vp, i64, vp, i64, i, vp]
+        L.bmsp_spsm_launch_info.argtypes = [vp, i, i, i, i, i64, i64, vp, p(SpsmInfo)]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -503,6 +515,10 @@ class BmSpMatrix:
         """x with op(tri(this)) * x = alpha * b: pybmsp.spsv"""
         return spsv(self, b, op, fill, unit_diag, alpha, x, stream)
 
+    def solve_triangular_multi(self, B, k, op="N", fill="lower", unit_diag=False, alpha=1.0, X=None, ldb=None, ldx=None, stream=None):
+        """X with op(tri(this)) * X = alpha * B for k right-hand sides: pybmsp.spsm"""
+        return spsm(self, B, k, op, fill, unit_diag, alpha, X, ldb, ldx, stream)
+
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
         return spgemm_masked(self, B, M, alpha, beta, mul_m, transposed, stream)
@@ -780,6 +796,53 @@ def spsv_plan(ptr, other, lower, chain):
                                level_of.ctypes.data, order.ctypes.data, level_ptr.ctypes.data, segments.ctypes.data, C.byref(nl),
                                C.byref(ns)))
     return level_of, order, level_ptr[:nl.value + 1].copy(), segments[:ns.value].copy()
+
+
+def _spsm_strides(k, ldb, ldx):
+    k = int(k)
+    ldb = k if ldb is None else int(ldb)
+    ldx = k if ldx is None else int(ldx)
+    if k < 1:
+        raise ValueError("k must be >= 1 (got %d)" % k)
+    if ldb < k or ldx < k:
+        raise ValueError("ldb and ldx must be >= k (got ldb = %d, ldx = %d, k = %d)" % (ldb, ldx, k))
+    return k, ldb, ldx
+
+
+def spsm(A, B, k, op="N", fill="lower", unit_diag=False, alpha=1.0, X=None, ldb=None, ldx=None, stream=None):
+    """Solves op(tri(A)) * X = alpha * B for k right-hand sides on the device (bmsp_spsm); op, fill and unit_diag as for spsv.  B:
+    DeviceArray (float32, float64 for F64), row-major num_rows x k at leading dimension ldb (default k); X: the same at leading dimension
+    ldx (default k), made as num_rows x ldx when None, and may be B itself (in place: ldx must then equal ldb).  Returns X.  Column c of X
+    holds the bits spsv writes for column c of B; one walk of the dependency chain carries all k columns.  Asynchronous on `stream` once
+    the plan of (A, op, fill) exists (spsv_analyse, spsm_launch_info, or the first solve)."""
+    o, f = _op(op), _fill(fill)
+    k, ldb, ldx = _spsm_strides(k, ldb, ldx)
+    i = A.info()
+    n = i["num_rows"]
+    vt = np.dtype(OUT_DTYPE[i["dtype"]])
+    need_b = (n - 1) * ldb + k if n else 0
+    if B.dtype != vt or B.n < need_b:
+        raise ValueError("B must hold %d entries of %s" % (need_b, vt.name))
+    if X is None:
+        X = DeviceArray(n * ldx, vt)
+    else:
+        need_x = (n - 1) * ldx + k if n else 0
+        if X.dtype != vt or X.n < need_x:
+            raise ValueError("X must hold %d entries of %s" % (need_x, vt.name))
+        if X is B and ldx != ldb:
+            raise ValueError("in place (X is B) needs ldx == ldb (got ldb = %d, ldx = %d)" % (ldb, ldx))
+    check(lib().bmsp_spsm(A.h, o, f, DIAG_UNIT if unit_diag else DIAG_NON_UNIT, float(alpha), B.ptr, ldb, X.ptr, ldx, k, stream))
+    return X
+
+
+def spsm_launch_info(A, op, fill, k, unit_diag=False, ldb=None, ldx=None, stream=None):
+    """{"kernel", "lanes", "col_chunks", "levels", "launches", "chain_launches", "chained_levels", "plan_bytes"} of the launches spsm(A, B,
+    k, op, fill) makes; builds the plan of (A, op, fill) if it is missing, which synchronises `stream` (bmsp_spsm_launch_info)."""
+    o, f = _op(op), _fill(fill)
+    k, ldb, ldx = _spsm_strides(k, ldb, ldx)
+    info = SpsmInfo()
+    check(lib().bmsp_spsm_launch_info(A.h, o, f, DIAG_UNIT if unit_diag else DIAG_NON_UNIT, k, ldb, ldx, stream, C.byref(info)))
+    return info.as_dict()
 
 
 def spmv_chunk_layout(A):

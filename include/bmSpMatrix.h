@@ -316,6 +316,23 @@ inline void bmSparse_SpSV_analyse(bmSpMatrix<ValueIn> &A, int op, int fill, int 
     bmsp::check(bmsp_spsv_analyse(A.handle(), op, fill, diag, nullptr, info));
 }
 
+/* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are
+ * device pointers to num_rows x k row-major arrays at leading dimensions ldb, ldx >= k (float, double for double); they may be the same
+ * when ldb == ldx.  Column c of X holds the bits bmSparse_SpSV writes for column c of B, for one walk of the dependency chain instead of
+ * k; synchronous like bmSparse_SpMV.  bmSparse_SpSM_launch_info reports what that call launches (it builds the shared plan if missing). */
+template <class ValueIn>
+inline void bmSparse_SpSM(bmSpMatrix<ValueIn> &A, const typename bmsp::vector_of<ValueIn>::type *B, int64_t ldb,
+                          typename bmsp::vector_of<ValueIn>::type *X, int64_t ldx, int k, int op, int fill, int diag, double alpha)
+{
+    bmsp::check(bmsp_spsm(A.handle(), op, fill, diag, alpha, B, ldb, X, ldx, k, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+template <class ValueIn>
+inline void bmSparse_SpSM_launch_info(bmSpMatrix<ValueIn> &A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, bmsp_spsm_info *info)
+{
+    bmsp::check(bmsp_spsm_launch_info(A.handle(), op, fill, diag, k, ldb, ldx, nullptr, info));
+}
+
 /* Multi-vector form: U = A * V for k vectors, V row-major num_cols x k, U row-major num_rows x k. */
 template <class ValueIn, class ValueOut> inline void bmSparse_SpMM(bmSpMatrix<ValueIn> &A, ValueIn *V, ValueOut *U, int k)
 {

@@ -410,6 +410,49 @@ int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, i
                    uint32_t *level_of, uint32_t *order, uint32_t *level_ptr, uint32_t *segments,
                    int64_t *n_levels, int64_t *n_segments);
 
+/* SpSM, the sparse triangular solve for k right-hand sides: op(tri(A)) * X = alpha * B, everything else as bmsp_spsv -- block Krylov
+ * methods, several Gauss-Seidel sweeps at once, the multi-vector application of an incomplete factor next to bmsp_spmm / bmsp_spmm_op.  A
+ * solve is a chain of dependent steps, not a stream of bytes, and k calls of bmsp_spsv pay the whole chain k times; the columns of B are
+ * independent, so one walk of the chain carries them all.  Nothing in the reference is replaced (it has no solve).
+ *   Operands: B and X are n x k, row-major, leading dimensions ldb >= k and ldx >= k (the convention of bmsp_spmm / bmsp_spmm_op),
+ *       elements of bmsp_spsv's vector type (float for F32 / F16, double for F64), aligned to their element type and no more.  op, fill and
+ *       diag mean exactly what they mean for bmsp_spsv; A may be in either tile layout.
+ *   Numerics, one sentence: column c of X holds, bit for bit, what bmsp_spsv(A, op, fill, diag, alpha, column c of B) writes -- s =
+ *       fl(alpha * b), one fma(-a_ij, x_j, s) per stored entry of the effective strict triangle in the order of a sequential substitution,
+ *       one IEEE division per row (the full sequence, never a reciprocal) or none under BMSP_DIAG_UNIT.  X is a pure function of A's
+ *       arrays, B and alpha: it does not depend on BMSP_SPSM_LANES, on BMSP_SPSV_CHAIN, on k, on the strides or on the stream.  Columns do
+ *       not mix: an Inf or NaN in one column of B never reaches another column of X.
+ *   Read and written: every X[i][c], i < n, c < k, is written (rows of block-rows without tiles too, under BMSP_DIAG_UNIT).  The padding
+ *       columns k <= c < ld of B are never read, those of X never written, no row at or beyond n of either is touched.  As in bmsp_spsv the
+ *       other triangle, the other-side entries of a diagonal tile and -- under BMSP_DIAG_UNIT -- the stored diagonal never reach X.  d_X ==
+ *       d_B with ldx == ldb is legal (in place); d_X == d_B with different strides is refused; any other overlap is the caller's error.
+ *   Plan: none of its own.  The call uses the cached bmsp_spsv plan of (op, fill) -- the same levels, order and launch schedule;
+ *       BMSP_SPSV_CHAIN keeps its meaning -- and builds it if it is missing, by the code bmsp_spsv uses (that build synchronises `stream`);
+ *       op T and column-major matrices use the cached view of bmsp_spmv_op, as bmsp_spsv does.  A plan built by bmsp_spsv / _spsv_analyse
+ *       serves bmsp_spsm and the other way round; it is dropped by the same events, and a value-only update needs no
+ *       bmsp_matrix_invalidate.  Once the plan exists the call is asynchronous on `stream`: launches only, no temporary, nothing read back.
+ *   Kernels (vector ALU): a lane owns ONE column of X for one block-row, all eight rows of it, as eight sums in registers; W lanes (W
+ *       columns) form a slot, a workgroup holds 256 / W slots (block-rows); the columns beyond W go to further column chunks, independent
+ *       of each other.  spsm_level_kernel: one launch per level, grid (ceil(width / slots), column chunks).  spsm_chain_kernel: one
+ *       workgroup per column chunk walks the levels of a chain launch, a workgroup barrier between levels.  No waiting between workgroups:
+ *       no flag, no spin, no atomic, no cooperative launch.  A slot's lanes read the same bitmap and values of a tile and load the rows of
+ *       X side by side; inside the diagonal tile a lane substitutes on its own.  W in {8, 16, 32, 64}: the smallest W >= min(k, 64), or
+ *       what BMSP_SPSM_LANES=8/16/32/64 forces (read per call; measured in DESIGN 4 "Triangular solve, several right-hand sides").
+ *   k == 1 with ldb == ldx == 1 IS bmsp_spsv: the call is handed over (as bmsp_spmm hands k = 1 to the SpMV).  n == 0 returns BMSP_OK
+ *       without a launch.
+ *   bmsp_spsm_launch_info: reporting only, from the function the launcher itself calls; builds the plan if it is missing, like the call.
+ *       kernel = the instantiation by name ("spsm_level_kernel<F32, MAJOR, LOWER, NON_UNIT, 32>": the first four as in bmsp_spsv_analyse,
+ *       then W; "bmsp_spsv: <bmsp_spsv_analyse's kernel name>" with lanes 8 and col_chunks 1 for the hand-off; "none (empty matrix)" for
+ *       n = 0), lanes = W, col_chunks = ceil(k / W); levels, launches, chain_launches, chained_levels and plan_bytes are those of the
+ *       shared plan (a launch covers all column chunks through the grid, so launches equals bmsp_spsv_analyse's).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing done on the device: op, fill or diag
+ *   not 0 / 1; k < 1, ldb < k, ldx < k; null A, d_B, d_X, info; num_rows != num_cols; row-panel views; d_X == d_B with ldb != ldx;
+ *   BMSP_DIAG_NON_UNIT with a row whose diagonal entry is not stored (bmsp_spsv's message).  BMSP_ERR_LIMIT: as for bmsp_spsv. */
+int bmsp_spsm(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_B, int64_t ldb, void *d_X, int64_t ldx, int k,
+              void *stream);
+typedef struct { char kernel[64]; int lanes, col_chunks; int64_t levels, launches, chain_launches, chained_levels, plan_bytes; } bmsp_spsm_info;
+int bmsp_spsm_launch_info(bmsp_matrix_t A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, void *stream, bmsp_spsm_info *info);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
