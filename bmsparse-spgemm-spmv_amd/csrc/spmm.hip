@@ -470,7 +470,9 @@ SpmmPath choose_path(bmsp_matrix_s *A, int k, int64_t ldx, int64_t ldy, hipStrea
     if (k == 1 && ldx == 1 && ldy == 1) return SpmmPath::kSpmv;  // one contiguous vector: the SpMV itself
     ensure_rowptr(A, st);
     build_plan(A, st);
-    prepare_spmv(A, st);  // + the position cache, for matrices the value-stream kernels take
+    // prepare_spmv builds what the SpMV of A reads AND, also where that SpMV takes the chunked sweep, the position cache: A->spmv_pos
+    // below is "the value-stream kernels take this matrix"
+    prepare_spmv(A, st);
     // measured on the webbase-1M-like case: the time is set by tiles x vector chunks (each wave walks its tiles
     // serially), so the widest lane group that k fills wins
     // k <= 8 on a matrix that carries the SpMV position cache (sparse tiles): the value-stream walk

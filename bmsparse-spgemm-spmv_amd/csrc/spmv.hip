@@ -4,12 +4,11 @@
 // block-row, one lane per tile ELEMENT, serial loop over the row's tiles) and spmv_kernel_new (:84-150, the "batched"
 // path: several tiles per step, wide lane reduction).  Both rebuild a block-row pointer on every call (:199-206).
 //
-// MI355X design (variant 0, the default): spmv_chunk_kernel for large fp32 matrices of sparse tiles (one wave per 512 stored values over
-// its own structure cache -- see its header below; BMSP_SPMV_NOCHUNK=1 keeps the value-stream kernel); otherwise the block-vector sweep
-// over a cached plan.  Three kernels share the plan; the launcher picks by
-// the matrix: spmv_vstream_kernel (lane per stored value; matrices of sparse tiles -- see its own header below), spmv_rowgroup_kernel
-// (16 lanes per block-row, 16-byte value loads; >= 16 values per tile and no hub block-row), spmv_sweep_kernel (lane per tile, described
-// here; since round 2 only its FULL-tile variant runs by default, BMSP_SPMV_OLD=1 brings the whole kernel back).
+// MI355X design: five kernel families -- spmv_blockrow_kernel (variants 1, 2 and matrices beyond the buffer descriptors' 4 GiB),
+// spmv_rowgroup_kernel (16 lanes per block-row, 16-byte value loads), spmv_chunk_kernel (one wave per 512 stored values over its own
+// structure cache), spmv_vstream_kernel (lane per stored value) and spmv_sweep_kernel (lane per tile).  Each has its header below; which
+// one runs for a matrix is decided in ONE place, choose() near the end of this file, where the table of path, condition and caches is.
+// All but the block-row kernels walk the cached sweep plan; spmv_sweep_kernel, described here, is the plan's first user:
 //   * A per-matrix SWEEP PLAN (built once, cached like the block-row pointer) cuts the block array into wave-sized
 //     work items.  Short block-rows are grouped into items aligned to block-row boundaries (<= 16 block-rows inside
 //     one aligned 16-row window, < 512 tiles; ~96 tiles for the value-stream kernel), so an item owns a contiguous slice of u outright.
@@ -38,7 +37,6 @@
 #include "spmv_plan.h"
 #include "prims.hip.h"
 #include <cstdlib>
-#include <cstring>
 #include <cstdio>
 #include <algorithm>
 #include <vector>
@@ -125,13 +123,6 @@ struct PlanFill {
             items[base].num_items = 0; items[base].long_idx = 0xffffffffu; items[base].val_begin = (uint32_t)rc.offsets[s];
         }
     }
-};
-
-struct SweepPlan {
-    SweepItem *items;
-    uint32_t num_items, num_long;
-    void *carry;         // num_items x 8 accumulators (only long items use their slot)
-    uint32_t *counters;  // num_long arrival counters, zero between calls
 };
 
 }  // namespace
@@ -1592,106 +1583,155 @@ void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
     A->spmv_cw_colbits = colbits;
 }
 
-// the chunked sweep takes (A, rows): variant 0, fp32, the whole matrix (no row range, no view), the value-stream kernel not asked for, and
-// (unless BMSP_SPMV_CHUNK=1 asks for it) fewer than 2 values per tile -- the run adds into LDS lose to the value-stream kernel's counting
-// sort on denser tiles (FEM-like 3.7 / tile 42.1 vs 28.6 us, cage-like 3.2 / tile 58.4 vs 56.6) -- and at least kChMinChunks chunks.
-// The cache must also fit (build_chunk_cache).
-bool chunk_wanted(const bmsp_matrix_s *A, uint32_t row_lo, uint32_t row_hi)
+// ---------------------------------------------------------------------------------------------------------
+// which kernel runs: decided in ONE place, for the launcher, bmsp_spmv_launch_info, bmsp_spmv_chunk_layout and bmsp_matrix_prepare
+// ---------------------------------------------------------------------------------------------------------
+// choose() walks this table from the top and takes the first row whose condition holds; it builds the caches of that row:
+//   path            condition                                                                              caches read
+//   none            no block-row                                                                           -
+//   block-row 64    variant 1 ("batched")                                                                  block-row pointer
+//   block-row 8     variant 2                                                                              block-row pointer
+//   block-row 64    values or x beyond the 4 GiB a buffer descriptor addresses                             block-row pointer
+//   row-group       variant 3; or variant 0 with >= 16 values per tile, no hub block-row and the kernel    block-row pointer (the plan is built
+//                   not switched off -- either way only on values from this library's allocator            for its count of hub block-rows)
+//   chunk           vstream_eligible, chunk_wanted, and the chunk cache fits the matrix                     chunk cache
+//   value-stream    vstream_eligible (mostly sparse tiles; red: kAtomic below 2 values per tile)            plan, position cache (kCached;
+//                                                                                                          kDecode where it was not built)
+//   sweep           the rest: <FULL> with a quarter of the tiles full, else the round-1 kernel             plan
+// The environment switches that steer the choice are read here (and in vstream_eligible / chunk_wanted, which only choose() and the plan
+// builder call), each at most once per call.
+enum class SpmvPath { kNone, kBlockRow64, kBlockRow8, kRowGroup, kChunk, kVstream, kSweep };
+enum class SweepKind { kFull, kPlain, kNT, kPersist };
+
+struct SpmvChoice {  // the path, the name bmsp_spmv_launch_info reports for it, and what its launch needs beyond the handle
+    SpmvPath path = SpmvPath::kNone;
+    const char *name = "none (empty matrix)";
+    bool cached = false; int red = kAtomic;  // value-stream: entries from the position cache (kCached) or decoded in the kernel; kAtomic / kSorted
+    int layout = 0;                          // chunk: 1 = words in storage order (round 7), 2 = row-sorted words
+    uint32_t passes = 1;                     // row-group: block-row groups per wave
+    SweepKind sweep = SweepKind::kPlain; int occ = 0; uint32_t grid = 0;  // sweep: the instantiation, which BMSP_SPMV_OCC=6 / 8 replaces by the one
+                                                                          // bound to that occupancy; workgroups (BMSP_SPMV_PERSIST caps them)
+};
+const char *path_name(const SpmvChoice &c) { return c.name; }
+
+// buffer descriptors address 4 GiB; a matrix whose values or x reach beyond goes to the pointer-based block-row kernel
+bool beyond_descriptors(const bmsp_matrix_s *A)
+{
+    const size_t es = dtype_size(A->dtype);
+    return (size_t)A->values_extent() * es >= (1ull << 32) || (size_t)A->num_cols * es >= (1ull << 32);
+}
+
+// the chunked sweep takes (A, rows): variant 0, fp32, the whole matrix (no row range, no view), the value-stream kernel not asked for
+// (red_forced: BMSP_SPMV_RED is set), and (unless BMSP_SPMV_CHUNK=1 asks for it) fewer than 2 values per tile -- the run adds into LDS lose
+// to the value-stream kernel's counting sort on denser tiles (FEM-like 3.7 / tile 42.1 vs 28.6 us, cage-like 3.2 / tile 58.4 vs 56.6) --
+// and at least kChMinChunks chunks.  The cache must also fit (build_chunk_cache).
+bool chunk_wanted(const bmsp_matrix_s *A, uint32_t row_lo, uint32_t row_hi, bool red_forced)
 {
     if (A->dtype != BMSP_F32 || row_lo != 0 || row_hi != (uint32_t)A->num_rows || A->view_values_end || A->view_block_begin) return false;
-    if (getenv("BMSP_SPMV_NOCHUNK") || getenv("BMSP_SPMV_NO_POSCACHE") || getenv("BMSP_SPMV_RED")) return false;
+    if (getenv("BMSP_SPMV_NOCHUNK") || getenv("BMSP_SPMV_NO_POSCACHE") || red_forced) return false;
     if (getenv("BMSP_SPMV_CHUNK")) return true;
     return A->nnz < 2 * A->block_num && (A->nnz + kChV - 1) / kChV >= kChMinChunks;
 }
 
+SpmvChoice choose(bmsp_matrix_s *A, int variant, uint32_t row_lo, uint32_t row_hi, hipStream_t st)
+{
+    SpmvChoice c;
+    const auto take = [&c](SpmvPath path, const char *name) { c.path = path; c.name = name; return c; };
+    const uint32_t nbr = (uint32_t)A->num_block_rows();
+    if (nbr == 0) return c;
+    if (variant == BMSP_SPMV_BATCHED) return take(SpmvPath::kBlockRow64, "spmv_blockrow_kernel<64 lanes per block-row>");
+    if (variant == 2) return take(SpmvPath::kBlockRow8, "spmv_blockrow_kernel<8 lanes per block-row>");
+    if (beyond_descriptors(A)) return take(SpmvPath::kBlockRow64, "spmv_blockrow_kernel<64 lanes per block-row>");
+    build_plan(A, st);
+    // dense tiles and no hub block-row: the row-group kernel streams the value array with 16-byte loads (variant 3); the 16-byte
+    // value loads may run 12 bytes past the last stored value: arrays from this library's allocator carry that slack
+    const bool dense_tiles = A->block_num > 0 && A->nnz >= 16 * A->block_num;
+    if ((variant == 3 || (variant == BMSP_SPMV_DEFAULT && dense_tiles && A->spmv_plan_long == 0 && !getenv("BMSP_SPMV_NO_ROWGROUP"))) && pool_owns(A->values)) {
+        const char *pe = getenv("BMSP_SPMV_PASSES");
+        c.passes = pe ? (uint32_t)std::max(1, atoi(pe)) : ((nbr + 3) / 4 > 32768 ? 2u : 1u);
+        return take(SpmvPath::kRowGroup, "spmv_rowgroup_kernel");
+    }
+    if (vstream_eligible(A)) {
+        const char *re = getenv("BMSP_SPMV_RED");
+        if (chunk_wanted(A, row_lo, row_hi, re != nullptr)) {
+            build_chunk_cache(A, st);
+            if (A->spmv_cw) { c.layout = A->spmv_cw_layout; return take(SpmvPath::kChunk, "spmv_chunk_kernel"); }
+        }
+        build_pos_cache(A, st);
+        c.cached = A->spmv_pos != nullptr;
+        c.red = re ? atoi(re) : (A->nnz < 2 * A->block_num ? kAtomic : kSorted);
+        return take(SpmvPath::kVstream, c.cached ? (c.red == kAtomic ? "spmv_vstream_kernel<kCached, kAtomic>" : "spmv_vstream_kernel<kCached, kSorted>")
+                                                 : (c.red == kAtomic ? "spmv_vstream_kernel<kDecode, kAtomic>" : "spmv_vstream_kernel<kDecode, kSorted>"));
+    }
+    const char *nt = getenv("BMSP_SPMV_NT"), *pers = getenv("BMSP_SPMV_PERSIST"), *occ = getenv("BMSP_SPMV_OCC");
+    const uint32_t n_items = (uint32_t)A->spmv_num_chunks;
+    c.sweep = A->spmv_full_tiles * 4 >= A->block_num ? SweepKind::kFull : (nt ? SweepKind::kNT : (pers ? SweepKind::kPersist : SweepKind::kPlain));
+    c.occ = occ ? atoi(occ) : 0;
+    c.grid = pers ? std::min<uint32_t>((n_items + 3) / 4, (uint32_t)atoi(pers)) : (n_items + 3) / 4;
+    return take(SpmvPath::kSweep, c.sweep == SweepKind::kFull ? "spmv_sweep_kernel<FULL>" : "spmv_sweep_kernel");  // (NT / PERSIST / OCC: the plain name)
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the launcher: casts and launches what choose() picked
+// ---------------------------------------------------------------------------------------------------------
 template <typename T>
 void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t st, uint32_t row_lo, uint32_t row_hi)
 {
     using Ac = typename Acc<T>::type;
-    uint32_t nbr = (uint32_t)A->num_block_rows();
-    if (nbr == 0) return;
-    if (variant == BMSP_SPMV_BATCHED) {
-        hipLaunchKernelGGL((spmv_blockrow_kernel<T, 64>), dim3((nbr + 3) / 4), dim3(kThreads), 0, st, A->rowptr, A->keys, A->bmps,
-                           A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, row_hi,
-                           (uint32_t)A->num_cols, nbr, row_lo);
-    } else if (variant == 2) {
-        hipLaunchKernelGGL((spmv_blockrow_kernel<T, 8>), dim3((nbr + 31) / 32), dim3(kThreads), 0, st, A->rowptr, A->keys, A->bmps,
-                           A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, row_hi,
-                           (uint32_t)A->num_cols, nbr, row_lo);
-    } else if ((size_t)A->values_extent() * sizeof(T) >= (1ull << 32) || (size_t)A->num_cols * sizeof(T) >= (1ull << 32)) {
-        // buffer descriptors address 4 GiB; beyond that fall back to the pointer-based block-row kernel
-        hipLaunchKernelGGL((spmv_blockrow_kernel<T, 64>), dim3((nbr + 3) / 4), dim3(kThreads), 0, st, A->rowptr, A->keys, A->bmps,
-                           A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, row_hi,
-                           (uint32_t)A->num_cols, nbr, row_lo);
-    } else {
-        build_plan(A, st);
-        // dense tiles and no hub block-row: the row-group kernel streams the value array with 16-byte loads (variant 3); the 16-byte
-        // value loads may run 12 bytes past the last stored value: arrays from this library's allocator carry that slack
-        const bool dense_tiles = A->block_num > 0 && A->nnz >= 16 * A->block_num;
-        if ((variant == 3 || (variant == BMSP_SPMV_DEFAULT && dense_tiles && A->spmv_plan_long == 0 && !getenv("BMSP_SPMV_NO_ROWGROUP"))) && pool_owns(A->values)) {
-            constexpr int U = 3;
-            const uint32_t groups = (nbr + 3) / 4;
-            const char *pe = getenv("BMSP_SPMV_PASSES");
-            const uint32_t passes = pe ? (uint32_t)std::max(1, atoi(pe)) : (groups > 32768 ? 2u : 1u);
-            const uint32_t waves = (groups + passes - 1) / passes;
-            hipLaunchKernelGGL((spmv_rowgroup_kernel<T, U>), dim3((waves + 3) / 4), dim3(kThreads), 0, st, A->rowptr, A->keys, A->bmps, A->offsets,
-                               (const T *)A->values, (const T *)v, (Ac *)u, row_hi, (uint32_t)A->num_cols, nbr,
-                               (uint32_t)((size_t)A->values_extent() * sizeof(T)) + 16u, passes, row_lo);
-            BMSP_CHECK_LAUNCH();
-            return;
-        }
-        const uint32_t n_items = (uint32_t)A->spmv_num_chunks;
-        char *mem = (char *)A->spmv_chunks;
-        if constexpr (std::is_same<T, float>::value) {
-            if (vstream_eligible(A) && chunk_wanted(A, row_lo, row_hi)) {
-                build_chunk_cache(A, st);
-                if (A->spmv_cw) {
-                    const char *cm = (const char *)A->spmv_cw;
-                    hipLaunchKernelGGL(A->spmv_cw_layout == 2 ? spmv_chunk_kernel<true> : spmv_chunk_kernel<false>, dim3((uint32_t)A->spmv_cw_chunks), dim3(64), 0, st, (const ChunkRec *)(cm + A->spmv_cw_off_rec),
-                                       (const uint32_t *)cm, (const float *)A->values, (const float *)v, (float *)u, (float *)(cm + A->spmv_cw_off_carry),
-                                       (uint32_t *)(cm + A->spmv_cw_off_cnt), (uint32_t)A->nnz, (uint32_t)A->num_rows, (uint32_t)A->num_cols,
-                                       (uint32_t)A->spmv_cw_colbits);
-                    BMSP_CHECK_LAUNCH();
-                    return;
-                }
-            }
-        }
-        if (vstream_eligible(A)) {
-            build_pos_cache(A, st);
-            const bool cached = A->spmv_pos != nullptr;
-            const char *re = getenv("BMSP_SPMV_RED");
-            const int red = re ? atoi(re) : (A->nnz < 2 * A->block_num ? kAtomic : kSorted);
-#define BMSP_VS_LAUNCH(MODE, RED)                                                                                                                \
-    hipLaunchKernelGGL((spmv_vstream_kernel<T, MODE, RED>), dim3(n_items), dim3(64), 0, st, (const SweepItem *)(mem + 64), n_items, A->keys, A->bmps, \
-                       A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, (Ac *)(mem + A->spmv_plan_off_carry),                             \
-                       (uint32_t *)(mem + A->spmv_plan_off_cnt), row_hi, (uint32_t)A->num_cols,                                                    \
-                       (uint32_t)((size_t)A->values_extent() * sizeof(T)), A->spmv_pos, (uint32_t)A->spmv_pos_base, (uint32_t)A->spmv_pos_count, row_lo,                     \
-                       A->spmv_tinfo, A->spmv_eoff)
-            if (cached && red == kAtomic) BMSP_VS_LAUNCH(kCached, kAtomic);
-            else if (cached) BMSP_VS_LAUNCH(kCached, kSorted);
-            else if (red == kAtomic) BMSP_VS_LAUNCH(kDecode, kAtomic);
-            else BMSP_VS_LAUNCH(kDecode, kSorted);
-            BMSP_CHECK_LAUNCH();
-            return;
-        }
-        const bool nt = getenv("BMSP_SPMV_NT") != nullptr;
-        const char *pers = getenv("BMSP_SPMV_PERSIST");
-        const char *occ = getenv("BMSP_SPMV_OCC");
-        auto kern = A->spmv_full_tiles * 4 >= A->block_num ? spmv_sweep_kernel<T, true, false> : (nt ? spmv_sweep_kernel<T, false, true> : (pers ? spmv_sweep_kernel<T, false, false, true> : spmv_sweep_kernel<T, false, false>));
-        if (occ && atoi(occ) == 6) kern = spmv_sweep_kernel<T, false, false, false, 6>;
-        if (occ && atoi(occ) == 8) kern = spmv_sweep_kernel<T, false, false, false, 8>;
-        const uint32_t grid = pers ? std::min<uint32_t>((n_items + 3) / 4, (uint32_t)atoi(pers)) : (n_items + 3) / 4;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), 0, st, (const SweepItem *)(mem + 64), n_items,
+    const SpmvChoice c = choose(A, variant, row_lo, row_hi, st);
+    const uint32_t nbr = (uint32_t)A->num_block_rows(), n_items = (uint32_t)A->spmv_num_chunks;
+    char *mem = (char *)A->spmv_chunks;
+    switch (c.path) {
+    case SpmvPath::kNone: return;
+    case SpmvPath::kBlockRow64:
+    case SpmvPath::kBlockRow8: {
+        const bool wave = c.path == SpmvPath::kBlockRow64;  // a wave per block-row: 4 per workgroup; 8 lanes per block-row: 32
+        hipLaunchKernelGGL((wave ? spmv_blockrow_kernel<T, 64> : spmv_blockrow_kernel<T, 8>), dim3(wave ? (nbr + 3) / 4 : (nbr + 31) / 32), dim3(kThreads), 0, st,
+                           A->rowptr, A->keys, A->bmps, A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, row_hi, (uint32_t)A->num_cols, nbr, row_lo);
+        break;
+    }
+    case SpmvPath::kRowGroup: {
+        const uint32_t groups = (nbr + 3) / 4, waves = (groups + c.passes - 1) / c.passes;
+        hipLaunchKernelGGL((spmv_rowgroup_kernel<T, /* U = */ 3>), dim3((waves + 3) / 4), dim3(kThreads), 0, st, A->rowptr, A->keys, A->bmps, A->offsets,
+                           (const T *)A->values, (const T *)v, (Ac *)u, row_hi, (uint32_t)A->num_cols, nbr,
+                           (uint32_t)((size_t)A->values_extent() * sizeof(T)) + 16u, c.passes, row_lo);
+        break;
+    }
+    case SpmvPath::kChunk: {  // (fp32 only: chunk_wanted)
+        const char *cm = (const char *)A->spmv_cw;
+        hipLaunchKernelGGL(c.layout == 2 ? spmv_chunk_kernel<true> : spmv_chunk_kernel<false>, dim3((uint32_t)A->spmv_cw_chunks), dim3(64), 0, st, (const ChunkRec *)(cm + A->spmv_cw_off_rec),
+                           (const uint32_t *)cm, (const float *)A->values, (const float *)v, (float *)u, (float *)(cm + A->spmv_cw_off_carry),
+                           (uint32_t *)(cm + A->spmv_cw_off_cnt), (uint32_t)A->nnz, (uint32_t)A->num_rows, (uint32_t)A->num_cols,
+                           (uint32_t)A->spmv_cw_colbits);
+        break;
+    }
+    case SpmvPath::kVstream: {
+        const auto kern = c.cached ? (c.red == kAtomic ? spmv_vstream_kernel<T, kCached, kAtomic> : spmv_vstream_kernel<T, kCached, kSorted>)
+                                   : (c.red == kAtomic ? spmv_vstream_kernel<T, kDecode, kAtomic> : spmv_vstream_kernel<T, kDecode, kSorted>);
+        hipLaunchKernelGGL(kern, dim3(n_items), dim3(64), 0, st, (const SweepItem *)(mem + 64), n_items, A->keys, A->bmps,
+                           A->offsets, (const T *)A->values, (const T *)v, (Ac *)u, (Ac *)(mem + A->spmv_plan_off_carry),
+                           (uint32_t *)(mem + A->spmv_plan_off_cnt), row_hi, (uint32_t)A->num_cols,
+                           (uint32_t)((size_t)A->values_extent() * sizeof(T)), A->spmv_pos, (uint32_t)A->spmv_pos_base, (uint32_t)A->spmv_pos_count, row_lo,
+                           A->spmv_tinfo, A->spmv_eoff);
+        break;
+    }
+    case SpmvPath::kSweep: {
+        auto kern = c.sweep == SweepKind::kFull ? spmv_sweep_kernel<T, true, false> : (c.sweep == SweepKind::kNT ? spmv_sweep_kernel<T, false, true> : (c.sweep == SweepKind::kPersist ? spmv_sweep_kernel<T, false, false, true> : spmv_sweep_kernel<T, false, false>));
+        if (c.occ == 6) kern = spmv_sweep_kernel<T, false, false, false, 6>;
+        if (c.occ == 8) kern = spmv_sweep_kernel<T, false, false, false, 8>;
+        hipLaunchKernelGGL(kern, dim3(c.grid), dim3(kThreads), 0, st, (const SweepItem *)(mem + 64), n_items,
                            A->keys, A->bmps, A->offsets, (const T *)A->values, (const T *)v, (Ac *)u,
                            (Ac *)(mem + A->spmv_plan_off_carry), (uint32_t *)(mem + A->spmv_plan_off_cnt), row_hi,
                            (uint32_t)A->num_cols, (uint32_t)((size_t)A->values_extent() * sizeof(T)), row_lo);
+        break;
+    }
     }
     BMSP_CHECK_LAUNCH();
 }
 
 }  // namespace
 
-// Which kernel bmsp_spmv launches for (A, variant) -- the launcher's own decisions, in its order -- and the bytes that kernel's layout
+// Which kernel bmsp_spmv launches for (A, variant) -- choose(), the launcher's own decision -- and the bytes that kernel's layout
 // must move per launch ("compulsory": every array it reads or writes, once; counted from the plan, not estimated):
 //   chunked sweep: value word + value per stored value (8 B) + chunk records (32 B) + x + y + per carry slot its 8 accumulators stored and
 //     read back + per folded block-row its counter (add + reset);
@@ -1700,6 +1740,7 @@ void launch(bmsp_matrix_s *A, const void *v, void *u, int variant, hipStream_t s
 //   value-stream, in-kernel decode: items + keys, bitmaps, offsets (24 B per tile) + values + x + y;
 //   row-group / block-row kernels: block-row pointer + 24 B per tile + values + x + y;   sweep: items + 24 B per tile + values + x + y.
 // format_bytes is SURVEY 8(d)'s figure for the bmSparse layout whatever the kernel reads: 24 B per tile + values + row pointer + x + y.
+// The read-backs of chunk records and plan items below belong to the reporting; choose() makes none.
 void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kernel, size_t kernel_cap, int64_t *compulsory, int64_t *format_bytes)
 {
     if (A->transposed) fail(BMSP_ERR_INVALID, "SpMV needs a matrix built with transposed=0");
@@ -1709,78 +1750,59 @@ void spmv_launch_info(bmsp_matrix_s *A, int variant, hipStream_t st, char *kerne
     const int64_t xy = es * A->num_cols + as * A->num_rows;
     const int64_t fmt = 24 * nb + es * nv + 4 * (nbr + 1) + xy;
     if (format_bytes) *format_bytes = fmt;
-    const char *name = "";
+    const SpmvChoice c = choose(A, variant, 0, (uint32_t)A->num_rows, st);
+    const int64_t n_items = A->spmv_num_chunks;
     int64_t bytes = fmt;
-    const bool wide = (size_t)A->values_extent() * (size_t)es >= (1ull << 32) || (size_t)A->num_cols * (size_t)es >= (1ull << 32);
-    if (nbr == 0) { name = "none (empty matrix)"; bytes = 0; }
-    else if (variant == BMSP_SPMV_BATCHED || wide) name = "spmv_blockrow_kernel<64 lanes per block-row>";
-    else if (variant == 2) name = "spmv_blockrow_kernel<8 lanes per block-row>";
-    else {
-        build_plan(A, st);
-        const bool dense_tiles = nb > 0 && nv >= 16 * nb;
-        if ((variant == 3 || (variant == BMSP_SPMV_DEFAULT && dense_tiles && A->spmv_plan_long == 0 && !getenv("BMSP_SPMV_NO_ROWGROUP"))) && pool_owns(A->values)) {
-            name = "spmv_rowgroup_kernel";
-        } else {
-            const int64_t n_items = A->spmv_num_chunks;
-            if (vstream_eligible(A) && chunk_wanted(A, 0, (uint32_t)A->num_rows)) build_chunk_cache(A, st);
-            if (vstream_eligible(A) && chunk_wanted(A, 0, (uint32_t)A->num_rows) && A->spmv_cw) {
-                // chunked sweep: value words + values (4 B each per stored value) + records + x + y + the carry slots of the folded
-                // block-rows (8 accumulators stored and read back per chunk that holds a part) and their counters (add + reset)
-                name = "spmv_chunk_kernel";
-                const int64_t nch = A->spmv_cw_chunks;
-                std::vector<ChunkRec> rec((size_t)nch);
-                BMSP_HIP(hipStreamSynchronize(st));
-                copy_d2h_staged(rec.data(), (const char *)A->spmv_cw + A->spmv_cw_off_rec, sizeof(ChunkRec) * (size_t)nch);
-                int64_t slots = 0;
-                for (const ChunkRec &r : rec) slots += ((r.flags & kChHead) ? 1 : 0) + ((r.flags & kChTail) ? 1 : 0);
-                bytes = 8 * nv + (int64_t)sizeof(ChunkRec) * nch + xy + 2 * 8 * as * slots + 8 * A->spmv_cw_split;
-            } else if (vstream_eligible(A)) {
-                build_pos_cache(A, st);
-                const bool cached = A->spmv_pos != nullptr;
-                const char *re = getenv("BMSP_SPMV_RED");
-                const int red = re ? atoi(re) : (nv < 2 * nb ? kAtomic : kSorted);
-                name = cached ? (red == kAtomic ? "spmv_vstream_kernel<kCached, kAtomic>" : "spmv_vstream_kernel<kCached, kSorted>")
-                              : (red == kAtomic ? "spmv_vstream_kernel<kDecode, kAtomic>" : "spmv_vstream_kernel<kDecode, kSorted>");
-                std::vector<SweepItem> items((size_t)n_items);
-                BMSP_HIP(hipStreamSynchronize(st));
-                if (n_items) copy_d2h_staged(items.data(), plan_items(A), sizeof(SweepItem) * (size_t)n_items);
-                int64_t multi_tiles = 0, long_items = 0;
-                for (const SweepItem &it : items) {
-                    if (!vs_single(it)) multi_tiles += (int64_t)(it.blk_end - it.blk_begin);
-                    if (it.num_items) long_items++;
-                }
-                bytes = 32 * n_items + xy + 64 * long_items + es * nv;
-                bytes += cached ? 4 * nb + 2 * multi_tiles + 2 * nv : 24 * nb;
-            } else {
-                name = A->spmv_full_tiles * 4 >= nb ? "spmv_sweep_kernel<FULL>" : "spmv_sweep_kernel";
-                bytes = 32 * n_items + 24 * nb + es * nv + xy;
-            }
-        }
+    switch (c.path) {
+    case SpmvPath::kNone: bytes = 0; break;
+    case SpmvPath::kBlockRow64: case SpmvPath::kBlockRow8: case SpmvPath::kRowGroup: break;
+    case SpmvPath::kChunk: {
+        // chunked sweep: value words + values (4 B each per stored value) + records + x + y + the carry slots of the folded
+        // block-rows (8 accumulators stored and read back per chunk that holds a part) and their counters (add + reset)
+        const int64_t nch = A->spmv_cw_chunks;
+        std::vector<ChunkRec> rec((size_t)nch);
+        BMSP_HIP(hipStreamSynchronize(st));
+        copy_d2h_staged(rec.data(), (const char *)A->spmv_cw + A->spmv_cw_off_rec, sizeof(ChunkRec) * (size_t)nch);
+        int64_t slots = 0;
+        for (const ChunkRec &r : rec) slots += ((r.flags & kChHead) ? 1 : 0) + ((r.flags & kChTail) ? 1 : 0);
+        bytes = 8 * nv + (int64_t)sizeof(ChunkRec) * nch + xy + 2 * 8 * as * slots + 8 * A->spmv_cw_split;
+        break;
     }
-    if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", name);
+    case SpmvPath::kVstream: {
+        std::vector<SweepItem> items((size_t)n_items);
+        BMSP_HIP(hipStreamSynchronize(st));
+        if (n_items) copy_d2h_staged(items.data(), plan_items(A), sizeof(SweepItem) * (size_t)n_items);
+        int64_t multi_tiles = 0, long_items = 0;
+        for (const SweepItem &it : items) {
+            if (!vs_single(it)) multi_tiles += (int64_t)(it.blk_end - it.blk_begin);
+            if (it.num_items) long_items++;
+        }
+        bytes = 32 * n_items + xy + 64 * long_items + es * nv;
+        bytes += c.cached ? 4 * nb + 2 * multi_tiles + 2 * nv : 24 * nb;
+        break;
+    }
+    case SpmvPath::kSweep: bytes = 32 * n_items + 24 * nb + es * nv + xy; break;
+    }
+    if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", path_name(c));
     if (compulsory) *compulsory = bytes;
 }
 
-// the layout of the chunk cache the sweep of A would read (built as spmv_launch_info builds it): 0 = no chunk cache (another kernel takes
-// A), 1 = words in storage order (round 7), 2 = row-sorted words
+// the layout of the chunk cache the default sweep of A reads (choose() builds it): 0 = no chunk cache (another kernel takes A), 1 = words
+// in storage order (round 7), 2 = row-sorted words
 int spmv_chunk_layout(bmsp_matrix_s *A, hipStream_t st)
 {
-    char name[64];
-    spmv_launch_info(A, BMSP_SPMV_DEFAULT, st, name, sizeof(name), nullptr, nullptr);
-    return strcmp(name, "spmv_chunk_kernel") == 0 ? A->spmv_cw_layout : 0;
+    if (A->transposed) fail(BMSP_ERR_INVALID, "SpMV needs a matrix built with transposed=0");
+    const SpmvChoice c = choose(A, BMSP_SPMV_DEFAULT, 0, (uint32_t)A->num_rows, st);
+    return c.path == SpmvPath::kChunk ? c.layout : 0;
 }
 
+// bmsp_matrix_prepare(BMSP_PREPARE_SPMV): everything the default sweep of the whole matrix reads -- choose() builds it.  Second purpose:
+// spmm.hip's choose_path() keys its value-stream kernels on A->spmv_pos, so a matrix whose SpMV takes the chunked sweep gets the position
+// cache as well (on the value-stream path choose() has built it; the row-group, sweep and block-row paths get none, SpMM's other kernels run)
 void prepare_spmv(bmsp_matrix_s *A, hipStream_t st)
 {
-    if (A->transposed || A->num_block_rows() == 0) return;
-    const size_t es = dtype_size(A->dtype);
-    if ((size_t)A->values_extent() * es >= (1ull << 32) || (size_t)A->num_cols * es >= (1ull << 32)) return;  // block-row kernel: no plan
-    build_plan(A, st);
-    const bool rowgroup = A->block_num > 0 && A->nnz >= 16 * A->block_num && A->spmv_plan_long == 0 && !getenv("BMSP_SPMV_NO_ROWGROUP") && pool_owns(A->values);
-    if (vstream_eligible(A) && !rowgroup) {
-        build_pos_cache(A, st);
-        if (chunk_wanted(A, 0, (uint32_t)A->num_rows)) build_chunk_cache(A, st);
-    }
+    if (A->transposed) return;
+    if (choose(A, BMSP_SPMV_DEFAULT, 0, (uint32_t)A->num_rows, st).path == SpmvPath::kChunk) build_pos_cache(A, st);
 }
 
 // row_lo / row_hi: only rows [row_lo, row_hi) of u are written (the sharded sweep: a rank writes its own slice and nothing else);

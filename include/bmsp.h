@@ -300,7 +300,8 @@ int bmsp_spmv(bmsp_matrix_t A, const void *d_v, void *d_u, int variant, void *st
 
 /* What bmsp_spmv(A, ..., variant, ...) launches and what that launch must move (the measurement contract of SURVEY 8(d): "if the build
  * stores a more compact internal layout, use that layout's compulsory bytes"): kernel_name receives the name of the kernel the launcher
- * picks for this matrix (the cached plan and position cache are built if they are not yet), *compulsory_bytes the bytes of every array
+ * picks for this matrix -- it shares the launcher's decision: one function makes it for both, and for bmsp_spmv_chunk_layout and
+ * bmsp_matrix_prepare -- (the cached plan and position cache are built if they are not yet), *compulsory_bytes the bytes of every array
  * that kernel reads or writes, each once, counted from the plan; *format_bytes the layout-independent figure 24 B per block + values +
  * block-row pointer + x + y.  Reporting only: no reference line to replace (the reference prints a time, src/bmSparse_SPMV.cu:306). */
 int bmsp_spmv_launch_info(bmsp_matrix_t A, int variant, char *kernel_name, size_t kernel_name_cap, int64_t *compulsory_bytes, int64_t *format_bytes);

@@ -22,6 +22,7 @@ Which calls are asynchronous, from include/bmsp.h (the sentence of the header ea
 
   call                                  contract   header sentence
   bmsp_spmv, plan cached                ASYNC      "Asynchronous on `stream` once the cached sweep plan of A exists"
+  bmsp_spmv, after bmsp_matrix_prepare  ASYNC      the same sentence: prepare builds the plan and every cache the default launch reads
   bmsp_spmv, first call                 SYNC       "the call that builds the plan, the position cache or the chunk cache ... synchronises"
   bmsp_spmv, first call, variants 1, 2  ASYNC      the same sentence: the block-row kernels need none of the three
   bmsp_spmm, first call                 SYNC       "the first product of a handle builds bmsp_spmv's plan and synchronises as that call does"
@@ -393,6 +394,12 @@ def spmv_case(launch, gated, phase, dtype):
             call(bmsp, o, None)
             if "chunk" in launch:
                 assert bmsp.spmv_chunk_layout(o.A) == (1 if env.get("BMSP_SPMV_CHUNK_SORTED") == "0" else 2)
+        if phase == "prepared":
+            # bmsp_matrix_prepare instead of a first call: it must build all the launcher then reads.  The kernel is pinned on a twin of the
+            # same structure -- the query on o.A itself would build whatever prepare had left out -- and on o.A by read(), after the call
+            twin = mat(bmsp, S, 0, dtype)
+            assert bmsp.spmv_launch_info(twin, variant)["kernel"].startswith(kernel), bmsp.spmv_launch_info(twin, variant)
+            o.A.prepare(1)
         if gated == "vals":
             o.A.invalidate(False)
 
@@ -400,19 +407,32 @@ def spmv_case(launch, gated, phase, dtype):
         assert bmsp.spmv_launch_info(o.A, variant)["kernel"].startswith(kernel), bmsp.spmv_launch_info(o.A, variant)
         return [o.y.to_host()]
 
-    sync = ASYNC if phase == "steady" or kernel.startswith("spmv_blockrow_kernel") else SYNC
+    sync = ASYNC if phase in ("steady", "prepared") or kernel.startswith("spmv_blockrow_kernel") else SYNC
     return Case("spmv-%s-%s-%s-%s" % (launch, gated, phase, DT[dtype]), sync, make, call, read, prepare, env=env)
 
 
 # (the chunked sweep is an fp32 kernel)
 SPMV_CASES = [spmv_case(l, "x", ph, dt) for l in ALL_SPMV for ph in ("first", "steady") for dt in (0, 1, 2) if dt == 0 or "chunk" not in l] + \
              [spmv_case(l, "vals", ph, 0) for l in ALL_SPMV for ph in ("first", "steady")]
+# after bmsp_matrix_prepare instead of a first call: every default-variant launch, in every dtype it exists for
+SPMV_PREPARED = {dt: [spmv_case(l, "x", "prepared", dt) for l in ALL_SPMV if ALL_SPMV[l][2] == 0 and (dt == 0 or "chunk" not in l)] for dt in (0, 1, 2)}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", SPMV_CASES, ids=ids(SPMV_CASES))
 def test_spmv(bmsp, monkeypatch, case):
     run_gated(bmsp, monkeypatch, case)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [0, 1, 2], ids=[DT[d] for d in (0, 1, 2)])
+def test_spmv_on_prepared_handles(bmsp, monkeypatch, dtype):
+    """bmsp_matrix_prepare builds exactly what the launcher then reads, on every path: the first bmsp_spmv of a prepared handle is
+    asynchronous.  One gated run per launch (the case's name is in every message), each under its own environment."""
+    assert SPMV_PREPARED[dtype]
+    for case in SPMV_PREPARED[dtype]:
+        with monkeypatch.context() as m:
+            assert run_gated(bmsp, m, case) == ASYNC, case.name
 
 
 # name -> (structure, BMSP_SPMM_NO_VSTREAM, k, kernel): the six launch paths as test_spmm.py pins them, on short and on long block-rows
