@@ -1340,7 +1340,7 @@ struct StructDiff {
 // The numeric stage alone (bmsp_spgemm_numeric): C already holds the structure of A x B -- from bmsp_spgemm or bmsp_spgemm_symbolic on
 // operands of the same structure -- and receives the values of A x B in place.  Where a strip kernel applies (it needs C's structure and
 // the operands, no task list) that is T_7 and nothing else; otherwise the whole product runs and its values are copied over after its
-// structure was checked against C's.
+// structure was checked against C's.  On every path C's value-derived caches are dropped before its values are written.
 void spgemm_numeric(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st, bmsp_spgemm_stats *stats)
 {
     if (!A || !B || !C) fail(BMSP_ERR_INVALID, "null argument");
@@ -1361,6 +1361,9 @@ void spgemm_numeric(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc
     const bool stamped = C->sp_a_hash != 0 && C->sp_b_hash != 0;
     if (stamped && (C->sp_a_hash != ensure_struct_hash(A, st) || C->sp_b_hash != ensure_struct_hash(B, st)))
         fail(BMSP_ERR_INVALID, "C holds the structure of a product of other operands (its stamp does not match A and B)");
+    // C is itself a valid left operand and may hold value-derived caches (CSR copy, lane / dense tiles, the finite flag) from a product it
+    // took part in: every path below rewrites its values, so they go first, as for every other in-place writer
+    drop_value_caches(C);
     if (stamped && C->block_num && strip_numeric && !(sf && sf[0] == '0') && mac_structure_numeric_ok(A, B, tc_version, st) && mac_strip_fits_c(C, st)) {
         StageTimer tm(st, true);
         tm.mark(-1);

@@ -118,7 +118,12 @@ int bmsp_matrix_arrays(bmsp_matrix_t m, uint64_t **d_keys, uint64_t **d_bmps, ui
  * keeps no derived state, so it always sees current values).  This engine caches derived structures on the handle: after writing
  * VALUES in place call bmsp_matrix_invalidate(m, 0) before the next product (drops the dense tile copies the block-MAC kernels read);
  * after changing keys / bitmaps / offsets call it with structure_changed = 1 (drops the block-row pointer, SpMV plan and position
- * cache, block records too).  Synchronises the device.  SpMV reads values directly: a value-only update needs no call for it. */
+ * cache, block records too).  Synchronises the device.  SpMV reads values directly: a value-only update needs no call for it.
+ * The library's own in-place writers need no call on their target: bmsp_matrix_copy_values, bmsp_matrix_add_values,
+ * bmsp_matrix_scale_values, bmsp_sddmm_values, bmsp_spgemm_masked_values and bmsp_spgemm_numeric (whose target is C) drop the target's
+ * value-derived caches themselves before they write.  Limitation: a row-panel view (bmsp_matrix_row_panel) holds caches of its own over
+ * its slice of the parent's values; a write to the parent, by the caller or by one of these calls, does not reach them -- make the
+ * views anew (or call bmsp_matrix_invalidate(view, 0)) after the parent's values changed. */
 int bmsp_matrix_invalidate(bmsp_matrix_t m, int structure_changed);
 /* Transpose and tile-layout conversion of a matrix already on the device (no COO round trip).  `out_transposed` is the layout of
  * the output's tiles, as the builders' flag: 0 row-major, 1 column-major (the right operand of bmsp_spgemm).  The output is a fresh
@@ -701,7 +706,9 @@ int bmsp_spgemm(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t *C, int mode, in
  *                         tc_version's block-MAC kernel from it (any value type).  Otherwise -- no kept list, or a C without a stamp
  *                         (adopted arrays) -- the whole product runs, its structure is checked against C's (BMSP_ERR_INVALID on a
  *                         mismatch) and its values are copied.  After changing an operand's values in place call
- *                         bmsp_matrix_invalidate(m, 0) first (cached tile copies); after changing its structure, (m, 1). */
+ *                         bmsp_matrix_invalidate(m, 0) first (cached tile copies); after changing its structure, (m, 1).  C itself
+ *                         needs no such call: bmsp_spgemm_numeric is one of the library's in-place writers and drops C's own
+ *                         value-derived caches (C is a valid left operand of a further product) before it writes C's values. */
 int bmsp_spgemm_symbolic(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t *C, int mode, int tc_version, void *stream,
                          bmsp_spgemm_stats *stats);
 int bmsp_spgemm_numeric(bmsp_matrix_t A, bmsp_matrix_t B, bmsp_matrix_t C, int tc_version, void *stream, bmsp_spgemm_stats *stats);
