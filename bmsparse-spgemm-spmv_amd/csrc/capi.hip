@@ -734,6 +734,19 @@ int bmsp_spsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const v
     BMSP_API_END
 }
 
+int bmsp_spitsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                double *delta_history, bmsp_spitsv_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    spitsv_check_args(op, fill, diag, max_iter, tol, flags, delta_history);
+    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
+    spsv_check_matrix(A);
+    spitsv_check_vectors(d_b, d_x);
+    load_kernels();
+    spitsv(A, op, fill, diag, alpha, d_b, d_x, max_iter, tol, flags, delta_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                    uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
 {

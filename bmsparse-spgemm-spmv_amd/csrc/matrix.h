@@ -115,6 +115,9 @@ struct bmsp_matrix_s {
     int64_t spmm_op_scratch_elems = 0, spmm_op_tmp_elems = 0;
     // bmsp_spsv: the plan per [op][fill], built by bmsp_spsv_analyse or the first solve; goes with the views (structure changes, free)
     bmsp_spsv_plan_s spsv_plans[2][2];
+    // bmsp_spitsv: the second iterate buffer, num_rows vector elements, made by the first call; goes with the plans (one stream per handle
+    // at a time: two calls on two streams would share it)
+    void *spitsv_tmp = nullptr;
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -297,6 +300,12 @@ void spsm_check_args(int op, int fill, int diag, int k, int64_t ldb, int64_t ldx
 void spsm_check_in_place(const void *B, int64_t ldb, const void *X, int64_t ldx);
 void spsm(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *B, int64_t ldb, void *X, int64_t ldx, int k, hipStream_t st);
 void spsm_launch_info(bmsp_matrix_s *A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, hipStream_t st, bmsp_spsm_info *info);
+// spitsv.hip: block-Jacobi sweeps towards the solution of op(tri(A)) * x = alpha * b on the plan of spsv.hip (built if it is missing, which
+// synchronises `st`), until the stop rule holds or max_iter sweeps have run
+void spitsv_check_args(int op, int fill, int diag, int64_t max_iter, double tol, int flags, const double *delta_history);
+void spitsv_check_vectors(const void *b, const void *x);
+void spitsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *b, void *x, int64_t max_iter, double tol, int flags,
+            double *delta_history, bmsp_spitsv_info *info, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -27,90 +27,6 @@ namespace {
 
 constexpr int kGroups = kThreads / 8;  // block-rows per workgroup and pass
 
-// Lane i of a group solves row i of output block I: every x the row depends on outside the block is final (an earlier launch, or an
-// earlier level of this workgroup behind a barrier).  b may be x (in place): a row's b is read by its own lane before that lane writes.
-template <typename S, bool MINOR, bool LOWER, bool UNIT>
-__device__ __forceinline__ void spsv_block_row(const SpsvTiles &T, const uint32_t *__restrict__ ptr, const S *__restrict__ vals,
-                                               typename TileValue<S>::R alpha, const typename TileValue<S>::R *b,
-                                               typename TileValue<S>::R *x, int64_t n, uint32_t I, int i)
-{
-#pragma clang fp contract(off)
-    using D = TileValue<S>;
-    using F = typename D::F;
-    const int64_t o = (int64_t)I * 8 + i;
-    const bool row = o < n;  // (the ragged last block: its rows beyond n store nothing and are not written)
-    F s = row ? alpha * b[o] : F(0);
-    int64_t t = LOWER ? (int64_t)ptr[I] : (int64_t)ptr[I + 1] - 1;
-    const int64_t end = LOWER ? (int64_t)ptr[I + 1] : (int64_t)ptr[I] - 1;
-    uint4 r = make_uint4(0u, 0u, 0u, 0u), next = r;
-    bool diag = false;
-    if (t != end) next = spsv_rec(T, (uint64_t)t);
-    for (; t != end; t += LOWER ? 1 : -1) {
-        r = next;
-        if (LOWER ? r.w >= I : r.w <= I) {  // the diagonal tile, or the first tile of the triangle that is not read
-            diag = r.w == I;
-            break;
-        }
-        // the next record of the block-row is on its way while this tile's values and x arrive (records do not depend on x)
-        const int64_t tn = t + (LOWER ? 1 : -1);
-        if (tn != end) next = spsv_rec(T, (uint64_t)tn);
-        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
-        const S *tv = vals + r.z;
-        const F *tx = x + (uint64_t)r.w * 8;  // only stored entries index it: never beyond the matrix
-        if (!MINOR) {
-            uint32_t byte = tile_byte(bmp, i);
-            if (LOWER) {
-                int k = tile_rank(bmp, 8 * i);
-                while (byte) {
-                    const int c = __builtin_clz(byte) - 24;
-                    byte &= ~(0x80u >> c);
-                    s = fused(-D::load(tv[k++]), tx[c], s);
-                }
-            } else {
-                int k = tile_rank(bmp, 8 * i) + __builtin_popcount(byte);
-                while (byte) {
-                    const int c = 7 - __builtin_ctz(byte);
-                    byte &= byte - 1;
-                    s = fused(-D::load(tv[--k]), tx[c], s);
-                }
-            }
-        } else {
-            uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
-            while (m) {
-                int p;
-                if (LOWER) p = tile_pop_first(m);
-                else { p = 63 - __builtin_ctzll(m); m &= m - 1; }
-                s = fused(-D::load(tv[tile_rank(bmp, p)]), tx[p >> 3], s);
-            }
-        }
-    }
-    F xi = s;  // no diagonal tile (unit diagonal): nothing inside the block
-    if (diag) {
-        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
-        const S *tv = vals + r.z;
-        F a[8], d = F(1);
-        uint32_t stored = 0;  // bit c: (i, c) lies in the strict triangle and is stored
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const int p = MINOR ? 8 * c + i : 8 * i + c;
-            a[c] = F(0);
-            if ((LOWER ? c < i : c > i) && tile_has(bmp, p)) {
-                a[c] = D::load(tv[tile_rank(bmp, p)]);
-                stored |= 1u << c;
-            }
-        }
-        if (!UNIT && tile_has(bmp, 9 * i)) d = D::load(tv[tile_rank(bmp, 9 * i)]);
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int c = LOWER ? k : 7 - k;
-            if (i == c) xi = UNIT ? s : s / d;
-            const F xc = __shfl(xi, c, 8);  // (the whole group is here: the walk above is the same for its eight lanes)
-            if ((stored >> c) & 1u) s = fused(-a[c], xc, s);
-        }
-    }
-    if (row) x[o] = xi;
-}
-
 // block-rows order[first .. first + width) of one level
 template <typename S, bool MINOR, bool LOWER, bool UNIT>
 __global__ __launch_bounds__(kThreads) void spsv_level_kernel(SpsvTiles T, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ order,
@@ -120,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void spsv_level_kernel(SpsvTiles T, const
 {
     const uint64_t g = ((uint64_t)blockIdx.x * kThreads + threadIdx.x) >> 3;
     if (g >= width) return;  // (whole groups leave: a shuffle stays inside its group)
-    spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, n, order[first + g], (int)(threadIdx.x & 7));
+    spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, x, n, order[first + g], (int)(threadIdx.x & 7));
 }
 
 // levels [l0, l1) by one workgroup; the level loop is uniform, the barrier orders the stores to x of a level before the loads of the next
@@ -135,7 +51,7 @@ __global__ __launch_bounds__(kThreads) void spsv_chain_kernel(SpsvTiles T, const
     for (uint32_t l = l0; l < l1; l++) {
         const uint64_t hi = level_ptr[l + 1];
         for (uint64_t k = (uint64_t)level_ptr[l] + g; k < hi; k += kGroups)
-            spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, n, order[k], i);
+            spsv_block_row<S, MINOR, LOWER, UNIT>(T, ptr, vals, alpha, b, x, x, n, order[k], i);
         __syncthreads();
     }
 }
@@ -203,6 +119,8 @@ void drop_spsv_plans(bmsp_matrix_s *m)
             pool_free(pl.mem);
             pl = bmsp_spsv_plan_s();
         }
+    pool_free(m->spitsv_tmp);
+    m->spitsv_tmp = nullptr;
 }
 
 // Levels and launch schedule of a substitution over `blocks` output blocks whose records [ptr[I], ptr[I + 1]) carry the other block

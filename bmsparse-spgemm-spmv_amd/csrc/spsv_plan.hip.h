@@ -1,6 +1,8 @@
-// spsv_plan.hip.h -- what the triangular solves share (spsv.hip: one right-hand side; spsm.hip: k of them): where the tile records of
-// (A, op) come from and how one is read, the fused multiply-add of the substitution, and the cached plan of (A, op, fill) -- its build
-// and the refusal it carries.  The kernels stay in their files: they differ in what a lane owns (a row there, a column of X here).
+// spsv_plan.hip.h -- what the triangular solves share (spsv.hip: one right-hand side; spsm.hip: k of them; spitsv.hip: block-Jacobi
+// sweeps): where the tile records of (A, op) come from and how one is read, the fused multiply-add of the substitution, the cached plan
+// of (A, op, fill) -- its build and the refusal it carries -- and the walk of one block-row by eight lanes (spsv_block_row: spsv.hip
+// with one vector, spitsv.hip with the previous and the next iterate).  The kernels stay in their files: they differ in what a lane
+// owns (a row there, a column of X in spsm.hip) and in what orders them (levels there, nothing in a sweep).
 #ifndef BMSP_SPSV_PLAN_HIP_H_
 #define BMSP_SPSV_PLAN_HIP_H_
 
@@ -29,6 +31,95 @@ __device__ __forceinline__ uint4 spsv_rec(const SpsvTiles &T, uint64_t t)
 
 __device__ __forceinline__ float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// Lane i of a group of eight computes row i of output block I and returns it (stored too when the row exists).  The x of the tiles off
+// the block diagonal is read from x_in, the row is written to x_out, inside the diagonal tile the group's new values go round by shuffle.
+//   substitution (spsv.hip): x_in == x_out; every x the row depends on outside the block is final (an earlier launch, or an earlier
+//       level of this workgroup behind a barrier).  b may be x (in place): a row's b is read by its own lane before that lane writes.
+//   sweep (spitsv.hip): x_in is the previous iterate, x_out the next one, two buffers -- exact inside the block, Jacobi between blocks.
+template <typename S, bool MINOR, bool LOWER, bool UNIT>
+__device__ __forceinline__ typename TileValue<S>::F spsv_block_row(const SpsvTiles &T, const uint32_t *__restrict__ ptr,
+                                                                   const S *__restrict__ vals, typename TileValue<S>::R alpha,
+                                                                   const typename TileValue<S>::R *b, const typename TileValue<S>::R *x_in,
+                                                                   typename TileValue<S>::R *x_out, int64_t n, uint32_t I, int i)
+{
+#pragma clang fp contract(off)
+    using D = TileValue<S>;
+    using F = typename D::F;
+    const int64_t o = (int64_t)I * 8 + i;
+    const bool row = o < n;  // (the ragged last block: its rows beyond n store nothing and are not written)
+    F s = row ? alpha * b[o] : F(0);
+    int64_t t = LOWER ? (int64_t)ptr[I] : (int64_t)ptr[I + 1] - 1;
+    const int64_t end = LOWER ? (int64_t)ptr[I + 1] : (int64_t)ptr[I] - 1;
+    uint4 r = make_uint4(0u, 0u, 0u, 0u), next = r;
+    bool diag = false;
+    if (t != end) next = spsv_rec(T, (uint64_t)t);
+    for (; t != end; t += LOWER ? 1 : -1) {
+        r = next;
+        if (LOWER ? r.w >= I : r.w <= I) {  // the diagonal tile, or the first tile of the triangle that is not read
+            diag = r.w == I;
+            break;
+        }
+        // the next record of the block-row is on its way while this tile's values and x arrive (records do not depend on x)
+        const int64_t tn = t + (LOWER ? 1 : -1);
+        if (tn != end) next = spsv_rec(T, (uint64_t)tn);
+        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
+        const S *tv = vals + r.z;
+        const F *tx = x_in + (uint64_t)r.w * 8;  // only stored entries index it: never beyond the matrix
+        if (!MINOR) {
+            uint32_t byte = tile_byte(bmp, i);
+            if (LOWER) {
+                int k = tile_rank(bmp, 8 * i);
+                while (byte) {
+                    const int c = __builtin_clz(byte) - 24;
+                    byte &= ~(0x80u >> c);
+                    s = fused(-D::load(tv[k++]), tx[c], s);
+                }
+            } else {
+                int k = tile_rank(bmp, 8 * i) + __builtin_popcount(byte);
+                while (byte) {
+                    const int c = 7 - __builtin_ctz(byte);
+                    byte &= byte - 1;
+                    s = fused(-D::load(tv[--k]), tx[c], s);
+                }
+            }
+        } else {
+            uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
+            while (m) {
+                int p;
+                if (LOWER) p = tile_pop_first(m);
+                else { p = 63 - __builtin_ctzll(m); m &= m - 1; }
+                s = fused(-D::load(tv[tile_rank(bmp, p)]), tx[p >> 3], s);
+            }
+        }
+    }
+    F xi = s;  // no diagonal tile (unit diagonal): nothing inside the block
+    if (diag) {
+        const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
+        const S *tv = vals + r.z;
+        F a[8], d = F(1);
+        uint32_t stored = 0;  // bit c: (i, c) lies in the strict triangle and is stored
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const int p = MINOR ? 8 * c + i : 8 * i + c;
+            a[c] = F(0);
+            if ((LOWER ? c < i : c > i) && tile_has(bmp, p)) {
+                a[c] = D::load(tv[tile_rank(bmp, p)]);
+                stored |= 1u << c;
+            }
+        }
+        if (!UNIT && tile_has(bmp, 9 * i)) d = D::load(tv[tile_rank(bmp, 9 * i)]);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int c = LOWER ? k : 7 - k;
+            if (i == c) xi = UNIT ? s : s / d;
+            const F xc = __shfl(xi, c, 8);  // (the whole group is here: the walk above is the same for its eight lanes)
+            if ((stored >> c) & 1u) s = fused(-a[c], xc, s);
+        }
+    }
+    if (row) x_out[o] = xi;
+    return xi;
+}
 
 // other[t] = the other block index of record t
 struct OtherColumn {

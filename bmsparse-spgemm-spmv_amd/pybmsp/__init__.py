@@ -27,6 +27,8 @@ SDDMM_MUL_S = 1
 MASKED_MUL_M = 1
 FILL_LOWER, FILL_UPPER = 0, 1
 DIAG_NON_UNIT, DIAG_UNIT = 0, 1
+ITSV_X0_GIVEN = 1
+ITSV_NO_CHECK = -1.0
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
@@ -41,7 +43,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -127,6 +129,16 @@ class SpsmInfo(C.Structure):
         return d
 
 
+class SpitsvInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("sweeps", C.c_int64), ("levels", C.c_int64), ("converged", C.c_int), ("delta", C.c_double),
+                ("xmax", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
 class ShardStats(C.Structure):
     _fields_ = [("world", C.c_int), ("rank", C.c_int), ("panel_block_row_begin", C.c_int64), ("panel_block_row_end", C.c_int64),
                 ("panel_tasks", C.c_int64), ("exchange_bytes", C.c_int64), ("exchange_us", C.c_double), ("exchange_exposed_us", C.c_double),
@@ -204,6 +216,7 @@ def lib():
         L.bmsp_spsv_plan.argtypes = [vp, vp, i64, i, i64, vp, vp, vp, vp, p(i64), p(i64)]
         L.bmsp_spsm.argtypes = [vp, i, i, i, C.c_double, vp, i64, vp, i64, i, vp]
         L.bmsp_spsm_launch_info.argtypes = [vp, i, i, i, i, i64, i64, vp, p(SpsmInfo)]
+        L.bmsp_spitsv.argtypes = [vp, i, i, i, C.c_double, vp, vp, i64, C.c_double, i, vp, p(SpitsvInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -519,6 +532,11 @@ class BmSpMatrix:
         """X with op(tri(this)) * X = alpha * B for k right-hand sides: pybmsp.spsm"""
         return spsm(self, B, k, op, fill, unit_diag, alpha, X, ldb, ldx, stream)
 
+    def solve_triangular_iterative(self, b, op="N", fill="lower", unit_diag=False, alpha=1.0, max_iter=0, tol=0.0, x=None, x0_given=False,
+                                   history=False, stream=None):
+        """block-Jacobi sweeps towards the x of op(tri(this)) * x = alpha * b: pybmsp.spitsv"""
+        return spitsv(self, b, op, fill, unit_diag, alpha, max_iter, tol, x, x0_given, history, stream)
+
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
         return spgemm_masked(self, B, M, alpha, beta, mul_m, transposed, stream)
@@ -796,6 +814,36 @@ def spsv_plan(ptr, other, lower, chain):
                                level_of.ctypes.data, order.ctypes.data, level_ptr.ctypes.data, segments.ctypes.data, C.byref(nl),
                                C.byref(ns)))
     return level_of, order, level_ptr[:nl.value + 1].copy(), segments[:ns.value].copy()
+
+
+def spitsv(A, b, op="N", fill="lower", unit_diag=False, alpha=1.0, max_iter=0, tol=0.0, x=None, x0_given=False, history=False, stream=None):
+    """Block-Jacobi sweeps towards the x of op(tri(A)) * x = alpha * b on the device (bmsp_spitsv); A, b, op, fill, unit_diag and alpha as
+    for spsv.  A sweep is one launch: exact inside every 8 x 8 diagonal tile, the previous iterate between block-rows; after `levels`
+    sweeps x holds spsv's bits.  Stops after a sweep that changed nothing or, with tol > 0, whose largest update is at most tol times the
+    largest |x_i|; max_iter=0 means levels + 1.  tol=ITSV_NO_CHECK runs exactly max_iter sweeps asynchronously, nothing read back (history
+    must be False).  x: DeviceArray for the result (made when None; never b); x0_given: x holds the initial iterate (default +0, x is not
+    read).  Returns (x, info) or (x, info, history): info = {"kernel", "sweeps", "levels", "converged", "delta", "xmax"}, history = the
+    delta of every sweep that ran (float64)."""
+    o, f = _op(op), _fill(fill)
+    i = A.info()
+    vt = np.dtype(OUT_DTYPE[i["dtype"]])
+    if b.dtype != vt or b.n < i["num_rows"]:
+        raise ValueError("b must hold %d entries of %s" % (i["num_rows"], vt.name))
+    if x is None:
+        if x0_given:
+            raise ValueError("x0_given needs x")
+        x = DeviceArray(i["num_rows"], vt)
+    elif x.dtype != vt or x.n < i["num_rows"]:
+        raise ValueError("x must hold %d entries of %s" % (i["num_rows"], vt.name))
+    info = SpitsvInfo()
+    hist = None
+    if history:
+        cap = int(max_iter) if max_iter else spsv_analyse(A, op, fill, unit_diag, stream)["levels"] + 1
+        hist = np.zeros(max(cap, 1), np.float64)
+    check(lib().bmsp_spitsv(A.h, o, f, DIAG_UNIT if unit_diag else DIAG_NON_UNIT, float(alpha), b.ptr, x.ptr, int(max_iter), float(tol),
+                            ITSV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info), stream))
+    d = info.as_dict()
+    return (x, d, hist[:d["sweeps"]].copy()) if history else (x, d)
 
 
 def _spsm_strides(k, ldb, ldx):

@@ -316,6 +316,19 @@ inline void bmSparse_SpSV_analyse(bmSpMatrix<ValueIn> &A, int op, int fill, int 
     bmsp::check(bmsp_spsv_analyse(A.handle(), op, fill, diag, nullptr, info));
 }
 
+/* Iterative triangular solve (bmsp_spitsv): block-Jacobi sweeps towards the x of bmSparse_SpSV's system; op, fill, diag, alpha, b and x as
+ * there, but x must not be b.  max_iter == 0 means levels + 1 of the plan (then tol == 0 returns bmSparse_SpSV's bits); tol > 0 stops at
+ * max |x_new - x_old| <= tol * max |x_new|; tol == BMSP_ITSV_NO_CHECK runs exactly max_iter sweeps with nothing read back.  flags:
+ * BMSP_ITSV_X0_GIVEN = x holds the initial iterate (default +0).  delta_history (host) and info may be null; synchronous like bmSparse_SpMV. */
+template <class ValueIn>
+inline void bmSparse_SpITSV(bmSpMatrix<ValueIn> &A, int op, int fill, int diag, double alpha, const typename bmsp::vector_of<ValueIn>::type *b,
+                            typename bmsp::vector_of<ValueIn>::type *x, int64_t max_iter = 0, double tol = 0.0, int flags = 0,
+                            double *delta_history = nullptr, bmsp_spitsv_info *info = nullptr)
+{
+    bmsp::check(bmsp_spitsv(A.handle(), op, fill, diag, alpha, b, x, max_iter, tol, flags, delta_history, info, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+
 /* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are
  * device pointers to num_rows x k row-major arrays at leading dimensions ldb, ldx >= k (float, double for double); they may be the same
  * when ldb == ldx.  Column c of X holds the bits bmSparse_SpSV writes for column c of B, for one walk of the dependency chain instead of

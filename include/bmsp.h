@@ -459,6 +459,70 @@ int bmsp_spsm(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const v
 typedef struct { char kernel[64]; int lanes, col_chunks; int64_t levels, launches, chain_launches, chained_levels, plan_bytes; } bmsp_spsm_info;
 int bmsp_spsm_launch_info(bmsp_matrix_t A, int op, int fill, int diag, int k, int64_t ldb, int64_t ldx, void *stream, bmsp_spsm_info *info);
 
+/* SpITSV, the iterative sparse triangular solve: block-Jacobi sweeps towards the x of op(tri(A)) * x = alpha * b -- the application of an
+ * incomplete factor or a Gauss-Seidel sweep inside a Krylov iteration, which needs the preconditioner's accuracy and not the exact
+ * substitution.  bmsp_spsv walks a dependency chain, `levels` dependent steps; a sweep is ONE launch over all block-rows with full
+ * parallelism, and a handful of sweeps reaches a useful accuracy.  Nothing in the reference is replaced (it has no solve).
+ *       x_I^{k+1} = T_II^{-1} * (alpha * b_I - sum over the tiles T_IJ, J != I, of the effective triangle of T_IJ * x_J^k)
+ * for every block-row I of eight rows: exact inside the 8 x 8 diagonal tile, Jacobi between block-rows.
+ *   Operands: A, op, fill, diag, alpha and the vector type of b and x are exactly bmsp_spsv's, both tile layouts, F32 / F16 / F64.  What
+ *       is never read is bmsp_spsv's too: the other triangle, the other-side entries of a diagonal tile and -- under BMSP_DIAG_UNIT -- the
+ *       stored diagonal.  A's four arrays and b are not modified.  d_x == d_b is refused: b is read in every sweep.
+ *   A sweep: every row runs bmsp_spsv's chain of operations -- s = fl(alpha * b_i); one s = fma(-a_ij, x_j, s) per stored entry of row i of
+ *       the effective strict triangle in chain order (ascending j for a lower system, descending for an upper one), x_j taken from the
+ *       PREVIOUS iterate when column j lies outside row i's own block of eight and from the NEW values inside it (those entries come last
+ *       in chain order); one IEEE division, or none under BMSP_DIAG_UNIT.  Every x_i, i < n, is written by every sweep, nothing at or
+ *       beyond n is.  The initial iterate is +0 and d_x is not read -- whatever it held, NaN included, never reaches x -- unless
+ *       BMSP_ITSV_X0_GIVEN is set in `flags`: then d_x holds x^0.
+ *   Finite termination: a block-row of plan level l (bmsp_spsv_analyse) holds bmsp_spsv's bits after sweep l + 1 and keeps them, so
+ *       after `levels` sweeps x is bit for bit bmsp_spsv's x, the only bitwise fixed point of the sweep.
+ *   Per-sweep statistics, order-independent and therefore deterministic: changed = some x_i differs in bits from the previous iterate;
+ *       delta = max_i |fl(x_i^{k+1} - x_i^k)| and xmax = max_i |x_i^{k+1}|, both in the vector type, NaNs skipped.
+ *   Stop rule, in the vector type with tol rounded once: stop after sweep k iff !changed || (tol > 0 && delta <= fl(tol * xmax)).
+ *       tol == 0 means "until nothing changes": with max_iter >= levels + 1 the call returns bmsp_spsv's bits.  max_iter == 0 means
+ *       levels + 1 of the cached plan.  x, sweeps and converged are a pure function of A's arrays, b, alpha, x^0, tol and max_iter: they do
+ *       not depend on the stream, on scheduling or on BMSP_SPITSV_CHECK.
+ *   Results: x in d_x.  delta_history (host, may be NULL): delta_history[k], k < sweeps, = sweep k's delta, widened exactly.  info (may be
+ *       NULL): the kernel instantiation by name ("spitsv_sweep_kernel<F32, MAJOR, LOWER, NON_UNIT, STATS>", the first four as in
+ *       bmsp_spsv_analyse, then STATS / NO_STATS; "none (empty matrix)" for n = 0), sweeps = the sweeps that ran, levels of the plan,
+ *       converged = the stop rule held at sweep `sweeps` (0: max_iter sweeps ran without it), and the last sweep's delta and xmax.
+ *   tol == BMSP_ITSV_NO_CHECK, the preconditioner mode: exactly max_iter sweeps (levels + 1 for 0) by a kernel instantiation without
+ *       statistics.  Once the plan and the handle's temporary exist the call is fully asynchronous on `stream`: launches and at most one
+ *       device copy, nothing read back, no pool temporary.  delta_history must be NULL; info gets sweeps = max_iter, converged = 0 and
+ *       delta = xmax = -1.
+ *   Plan and buffers: the cached plan of (A, op, fill) is bmsp_spsv's own -- built if missing (that synchronises `stream`), shared with
+ *       bmsp_spsv / bmsp_spsm, dropped by the same events; only its `levels` and its missing-diagonal row are used, a sweep has no
+ *       schedule.  Values are read at every call: a value-only update needs no bmsp_matrix_invalidate.  The iterates ping-pong between d_x
+ *       and ONE temporary of n vector elements kept on the handle (made by the first call, freed with the plans and with the handle); if
+ *       the last iterate sits in the temporary one asynchronous device copy moves it to d_x.  Because of that temporary, calls of ONE
+ *       handle must not overlap on different streams.
+ *   Kernel (vector ALU): spitsv_sweep_kernel, one launch per sweep, eight lanes per block-row, 32 block-rows per workgroup, block-rows
+ *       in natural order, tile records read one ahead, bmsp_spsv's lane mapping and in-tile substitution.  With statistics: reduced
+ *       across the wave in registers and across the workgroup in LDS, then at most one integer atomic max / or per workgroup and statistic
+ *       into the sweep's own record (the bits of a non-negative float order like an unsigned integer: no floating-point atomic).  Sweep
+ *       k + 1 begins by evaluating the stop rule on record k and returns without writing if it holds; the host enqueues
+ *       BMSP_SPITSV_CHECK=<sweeps> sweeps (read per call, default 8), reads the records back and decides by the same predicate.  A checked
+ *       call therefore synchronises `stream` once per BMSP_SPITSV_CHECK sweeps.  Long block-rows are not split (the chain order is the
+ *       contract): a hub block-row of thousands of tiles is one lane group's serial chain and bounds the sweep -- see README.
+ *   Measured (one MI355X, fp32, L = tril(A) + dominant diagonal, (N, lower); tools/spitsv_bench.py, DESIGN 4 "Iterative triangular solve"):
+ *       banded half-bandwidth 32, 2^17 rows, 16 384 levels: a sweep 8.8 us (bmsp_spmv on the triangle 7.7 us, bmsp_spsv 92.3 ms); the call
+ *       to 2^-10 5 sweeps / 124 us, to 2^-20 9 sweeps / 217 us, to the bitwise fixed point 66 sweeps / 1.19 ms.  fem_like 27pt, 12 380
+ *       levels: a sweep 17.6 us, 2^-10 9 sweeps / 259 us, 2^-20 17 sweeps / 432 us (bmsp_spsv 129.0 ms).  Hub block-rows: webbase-1M-like
+ *       (R-MAT 2^20 x 2, 376 levels) a sweep 1.17 ms against 16.6 us of bmsp_spmv, 2^-10 12 sweeps / 14.3 ms, 2^-20 18 sweeps / 21.5 ms
+ *       (bmsp_spsv 43.7 ms: 3.0x / 2.0x, a gain and no more); R-MAT 2^16 x 8 (254 levels) a sweep 0.39 ms, 4.3 / 6.1 ms against 16.5 ms.
+ *       BMSP_SPITSV_CHECK on the band at 2^-10: 199.5 / 134.7 / 120.6 / 138.3 / 255.9 us for 1 / 4 / 8 / 16 / everything at once.
+ *   n == 0 returns BMSP_OK without a launch (info: sweeps 0).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing done on the device: op, fill or diag
+ *   not 0 / 1; max_iter < 0 or > 2^20; tol NaN, or negative and not BMSP_ITSV_NO_CHECK; flags with a bit other than BMSP_ITSV_X0_GIVEN;
+ *   delta_history given under BMSP_ITSV_NO_CHECK; null A, d_b, d_x; num_rows != num_cols; row-panel views; d_x == d_b;
+ *   BMSP_DIAG_NON_UNIT with a row whose diagonal entry is not stored (bmsp_spsv's message).  BMSP_ERR_LIMIT: as for bmsp_spsv. */
+#define BMSP_ITSV_X0_GIVEN 1        /* flags bit 0: d_x holds the initial iterate (default: x^0 = +0, d_x is not read) */
+#define BMSP_ITSV_NO_CHECK (-1.0)   /* tol: run exactly max_iter sweeps, nothing read back */
+typedef struct { char kernel[64]; int64_t sweeps, levels; int converged; double delta, xmax; } bmsp_spitsv_info;
+int bmsp_spitsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const void *d_b, void *d_x,
+                int64_t max_iter, double tol, int flags, double *delta_history /* host, may be NULL */,
+                bmsp_spitsv_info *info /* may be NULL */, void *stream);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
