@@ -379,7 +379,7 @@ __global__ __launch_bounds__(kThreads) void rowmerge_build_kernel(TaskListArgs g
         n += (uint32_t)__popcll(__ballot(fresh));
         return true;
     });
-    if (!done || n > kTlCap) {
+    if (!done || n > kTlCap || ns + 64u > 65535u) {  // (the same bound on the surviving pairs whether or not a step followed the last of them)
         if (lane == 0) { g.cnt[row] = 0u; g.surv[row] = 0u; g.nnz[row] = 0u; atomicOr(g.overflow, 1u); }
         return;
     }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(64 * kBwWaves) void rowmerge_build_wg_kernel(TaskLi
     if (lane == 0) atomicAdd(&S.n_surv, ns);
     __syncthreads();
     const uint32_t n = S.n_cols, ns_all = S.n_surv;
-    if (S.abort_flag != 0u || n > kTlCap || ns_all > 65535u) {  // (task offsets inside a block-row are kept in 16 bits)
+    if (S.abort_flag != 0u || n > kTlCap || ns_all + 64u > 65535u) {  // (task offsets inside a block-row are kept in 16 bits; the one-wave form's bound)
         if (tid == 0) { g.cnt[row] = 0u; g.surv[row] = 0u; g.nnz[row] = 0u; atomicOr(g.overflow, 1u); }
         return;
     }
@@ -917,7 +917,7 @@ struct SetU32 {
 }  // namespace
 
 // C's structure AND the sorted task list of A x B by the build pass and the copy pass.  first_pos = T_2's exclusive scan of the fan-out
-// per A tile.  false: some block-row of C holds more tiles (or a block-row more than 65535 surviving pairs) than the pass accepts --
+// per A tile.  false: some block-row of C holds more tiles (or a block-row more than 65535 - 64 surviving pairs, in either build form) than the pass accepts --
 // nothing of C was allocated.  true: C->keys / bmps / rowptr / block_num / max_row_blocks are set; tasks = the surviving pairs
 // ((A tile << 32) | B tile) grouped by C tile in C's key order, inside a tile in ascending A tile; task_begin[c] = first task of C tile
 // c (c_size + 1 entries); c_of_wave[w] = C tile of task 64 w.
