@@ -420,6 +420,8 @@ void drop_spmv_op_views(bmsp_matrix_s *m)
     pool_free(m->spmv_op_tmp); m->spmv_op_tmp = nullptr;
     pool_free(m->spmm_op_scratch); m->spmm_op_scratch = nullptr; m->spmm_op_scratch_elems = 0;
     pool_free(m->spmm_op_tmp); m->spmm_op_tmp = nullptr; m->spmm_op_tmp_elems = 0;
+    pool_free(m->ilu0_diag); m->ilu0_diag = nullptr; m->ilu0_missing_row = -2;
+    pool_free(m->ilu0_tmp); m->ilu0_tmp = nullptr;
 }
 
 void alloc_tile_arrays(bmsp_matrix_s *m, uint64_t nb)

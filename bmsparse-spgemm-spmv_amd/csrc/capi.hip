@@ -747,6 +747,32 @@ int bmsp_spitsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const
     BMSP_API_END
 }
 
+int bmsp_matrix_ilu0(bmsp_matrix_t A, int64_t max_iter, double tol, int out_transposed, void *stream, bmsp_matrix_t *F, double *delta_history,
+                     bmsp_ilu0_info *info)
+{
+    BMSP_API_BEGIN
+    ilu0_check_args(max_iter, tol, delta_history);
+    check_layout_flag(out_transposed, "out_transposed");
+    need(A, "matrix A"); need(F, "F");
+    ilu0_check_matrices(A, nullptr);
+    load_kernels();
+    *F = ilu0_matrix(A, max_iter, tol, out_transposed, as_stream(stream), delta_history, info);
+    BMSP_API_END
+}
+
+int bmsp_matrix_ilu0_values(bmsp_matrix_t A, bmsp_matrix_t F, int64_t max_iter, double tol, int flags, void *stream, double *delta_history,
+                            bmsp_ilu0_info *info)
+{
+    BMSP_API_BEGIN
+    ilu0_check_args(max_iter, tol, delta_history);
+    ilu0_check_flags(flags);
+    need(A, "matrix A"); need(F, "matrix F");
+    ilu0_check_matrices(A, F);
+    load_kernels();
+    ilu0_values_into(A, F, max_iter, tol, flags, as_stream(stream), delta_history, info);
+    BMSP_API_END
+}
+
 int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                    uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
 {

@@ -118,6 +118,12 @@ struct bmsp_matrix_s {
     // bmsp_spitsv: the second iterate buffer, num_rows vector elements, made by the first call; goes with the plans (one stream per handle
     // at a time: two calls on two streams would share it)
     void *spitsv_tmp = nullptr;
+    // bmsp_matrix_ilu0 (ilu0.hip), on the factor F: the value index of every (j, j), num_rows entries, structure only; the first row
+    // whose diagonal entry is not stored (-1: none; -2: not looked yet); the second iterate buffer, nnz storage elements.  They go with
+    // the op-T view the sweeps walk (drop_spmv_op_views); one stream per handle at a time, as for spitsv_tmp.
+    uint32_t *ilu0_diag = nullptr;
+    int64_t ilu0_missing_row = -2;
+    void *ilu0_tmp = nullptr;
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -306,6 +312,16 @@ void spitsv_check_args(int op, int fill, int diag, int64_t max_iter, double tol,
 void spitsv_check_vectors(const void *b, const void *x);
 void spitsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void *b, void *x, int64_t max_iter, double tol, int flags,
             double *delta_history, bmsp_spitsv_info *info, hipStream_t st);
+// ilu0.hip: the incomplete factorisation ILU(0) of A by fixed-point sweeps, as a new matrix of A's structure (tiles in layout
+// out_transposed) or into a matrix made from A by ilu0_matrix or a layout-keeping maker.  Both build F's op-T view and diagonal index if
+// they are missing, which synchronises `st`.
+void ilu0_check_args(int64_t max_iter, double tol, const double *delta_history);
+void ilu0_check_flags(int flags);
+void ilu0_check_matrices(const bmsp_matrix_s *A, const bmsp_matrix_s *F);
+bmsp_matrix_s *ilu0_matrix(bmsp_matrix_s *A, int64_t max_iter, double tol, int out_transposed, hipStream_t st, double *delta_history,
+                           bmsp_ilu0_info *info);
+void ilu0_values_into(bmsp_matrix_s *A, bmsp_matrix_s *F, int64_t max_iter, double tol, int flags, hipStream_t st, double *delta_history,
+                      bmsp_ilu0_info *info);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -12,11 +12,11 @@
 //   spgemm_masked_kernel<SA, SM, G>  vector ALU, operands of storage type SA, mask and output of SM.  G lanes per M tile (lane_group,
 //                  tile_pass.hip.h).  The unit of work is one byte of the output bitmap (a row of a row-major output tile, a column of a
 //                  column-major one): G = 8 gives lane t byte t, G = 1 lets the lane visit its tile's non-empty bytes one after another.
-//                  Per unit a lane walks the intersection of A's block-row I with B's block-column J (walk_pairs) in ascending K and keeps
+//                  Per unit a lane walks the intersection of A's block-row I with B's block-column J (walk_pairs, walk_pairs.hip.h) in ascending K and keeps
 //                  the byte's eight accumulators in registers; the loop over the eight positions is fully unrolled and predicated by the
 //                  bitmap.  The eight lanes of a group issue the same list and record loads; they diverge only on their byte's positions.
 //   spgemm_masked_count_kernel       the same walk, counting the matches of every M tile (bmsp_spgemm_masked_launch_info's `pairs`).
-#include "tile_pass.hip.h"
+#include "walk_pairs.hip.h"
 #include <cstring>
 #include <vector>
 
@@ -30,120 +30,6 @@ constexpr int64_t kFillThreshold = 0;
 
 __device__ __forceinline__ float fma_f(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_f(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// The two candidate lists of an M tile, as sequences of entries with an inner block index `k` and whatever a match needs of the tile --
-// loaded with the index in one go, so that nothing is fetched after a match is known.
-//   A's block-row: tiles [lo, hi) of A, block columns ascending.  FULL = false (the counting walk) loads the key alone.
-template <bool FULL>
-struct ListA {
-    struct Entry {
-        uint32_t k;
-        uint64_t bmp, off;
-    };
-    const uint64_t *__restrict__ keys, *__restrict__ bmps, *__restrict__ offsets;
-    __device__ __forceinline__ Entry load(uint32_t i) const
-    {
-        Entry e;
-        e.k = key_col(keys[i]);
-        e.bmp = FULL ? bmps[i] : 0;
-        e.off = FULL ? offsets[i] : 0;
-        return e;
-    }
-};
-//   B's block-column: records [lo, hi) of B's op-T view {bitmap lo, hi, value offset, block-row}, block-rows ascending
-struct ListB {
-    struct Entry {
-        uint32_t k;
-        uint64_t bmp, off;
-    };
-    const uint4 *__restrict__ recs;
-    __device__ __forceinline__ Entry load(uint32_t i) const
-    {
-        const uint4 r = recs[i];
-        Entry e;
-        e.k = r.w;
-        e.bmp = (uint64_t)r.y << 32 | r.x;
-        e.off = r.z;
-        return e;
-    }
-};
-
-// Lower bound of k in list[left, hi), searched from the left end: probes at distance 1, 2, 4, .. until an entry is not below k, then
-// halvings inside the last step -- 2 * log2(distance) loads, one load when the next match is the next entry (lists of like length).
-// Returns the index; found = list[index].k == k, and then `hit` is that entry (the last probe that was not below k).  Both loops are
-// bounded by 32.
-template <typename L>
-__device__ __forceinline__ uint32_t lower_bound_from(const L &list, uint32_t left, uint32_t hi, uint32_t k, typename L::Entry &hit, bool &found)
-{
-    uint32_t lo = left, end = hi, step = 1;
-    bool have = false;
-    for (int s = 0; s < 32 && lo < end; s++) {
-        const uint32_t room = end - lo;
-        const uint32_t p = lo + (step < room ? step : room) - 1;
-        const typename L::Entry e = list.load(p);
-        if (e.k < k) {
-            lo = p + 1;
-            step <<= 1;
-        } else {
-            end = p;
-            hit = e;
-            have = true;
-            break;
-        }
-    }
-    for (int s = 0; s < 32 && lo < end; s++) {
-        const uint32_t mid = lo + ((end - lo) >> 1);
-        const typename L::Entry e = list.load(mid);
-        if (e.k < k) lo = mid + 1;
-        else {
-            end = mid;
-            hit = e;
-        }
-    }
-    found = have && hit.k == k;
-    return lo;
-}
-
-// fn(a, b) for every pair of an entry of A's block-row [a_lo, a_hi) and an entry of B's block-column [b_lo, b_hi) with the same inner
-// block index, in ascending order of that index.  The shorter list is walked, its next entry loaded one step ahead; each entry is found
-// in the longer list by lower_bound_from, whose left end carries forward from the previous hit: min * log(max / min) loads and not a walk
-// of both lists.  Every loop is bounded by a list length (the searches by 32).
-template <typename LA, typename Fn>
-__device__ __forceinline__ void walk_pairs(const LA &la, uint32_t a_lo, uint32_t a_hi, const ListB &lb, uint32_t b_lo, uint32_t b_hi, Fn &&fn)
-{
-    if (a_lo >= a_hi || b_lo >= b_hi) return;
-    if (a_hi - a_lo <= b_hi - b_lo) {
-        uint32_t left = b_lo;
-        typename LA::Entry next = la.load(a_lo);
-        for (uint32_t a = a_lo; a < a_hi; a++) {
-            const typename LA::Entry cur = next;
-            next = la.load(a + 1 < a_hi ? a + 1 : a);
-            if (left >= b_hi) break;
-            ListB::Entry hit;
-            bool found;
-            left = lower_bound_from(lb, left, b_hi, cur.k, hit, found);
-            if (found) {
-                fn(cur, hit);
-                left++;
-            }
-        }
-    } else {
-        uint32_t left = a_lo;
-        ListB::Entry next = lb.load(b_lo);
-        for (uint32_t b = b_lo; b < b_hi; b++) {
-            const ListB::Entry cur = next;
-            next = lb.load(b + 1 < b_hi ? b + 1 : b);
-            if (left >= a_hi) break;
-            typename LA::Entry hit;
-            bool found;
-            left = lower_bound_from(la, left, a_hi, cur.k, hit, found);
-            if (found) {
-                fn(hit, cur);
-                left++;
-            }
-        }
-    }
-}
 
 // what the kernels read of the three matrices (device pointers; the view's records and block-column pointer for B)
 template <typename SA>

@@ -17,8 +17,10 @@
 //       returns without writing when it holds; its own record stays zero, "nothing changed", so every later sweep returns too.  The host
 //       enqueues BMSP_SPITSV_CHECK sweeps, reads their records back and evaluates the same predicate: the switch decides how much is
 //       enqueued ahead, never the result.
+//   The record, the stop rule and the reduction live in sweep_stats.hip.h: ilu0.hip's sweeps end the same way.
 // The iterates ping-pong between d_x and one temporary kept on the handle; whichever holds the last one, it ends in d_x.
 #include "spsv_plan.hip.h"
+#include "sweep_stats.hip.h"
 #include <cmath>
 
 namespace bmsp {
@@ -27,44 +29,6 @@ namespace {
 constexpr int64_t kMaxIter = 1ll << 20;
 // Sweeps enqueued between two read-backs (BMSP_SPITSV_CHECK; measured in DESIGN §4 "Iterative triangular solve")
 constexpr int64_t kCheckDefault = 8;
-
-// One sweep's statistics: the bits of max |x_new - x_old| and of max |x_new| in the vector type (widened to 64 bits), and whether any
-// x_i changed in bits.  All zero = the sweep did not run.
-struct SweepRecord {
-    unsigned long long delta, xmax, changed, pad;
-};
-
-template <typename R>
-struct VecBits;
-template <>
-struct VecBits<float> {
-    static __host__ __device__ float from(unsigned long long u) { return __builtin_bit_cast(float, (uint32_t)u); }
-};
-template <>
-struct VecBits<double> {
-    static __host__ __device__ double from(unsigned long long u) { return __builtin_bit_cast(double, (uint64_t)u); }
-};
-
-// stop after the sweep of record r iff nothing changed, or (tol > 0 and) delta <= fl(tol * xmax): in the vector type, tol rounded once
-template <typename R>
-__host__ __device__ __forceinline__ bool stop_rule(const SweepRecord &r, R tol)
-{
-#pragma clang fp contract(off)
-    if (!r.changed) return true;
-    if (!(tol > R(0))) return false;
-    const R bound = tol * VecBits<R>::from(r.xmax);
-    return VecBits<R>::from(r.delta) <= bound;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // One sweep over block-rows [0, blocks).  prev: the record of the sweep before (null for the first), mine: this sweep's.
 template <typename S, bool MINOR, bool LOWER, bool UNIT, bool STATS>
@@ -92,28 +56,7 @@ __global__ __launch_bounds__(kThreads) void spitsv_sweep_kernel(SpsvTiles T, con
         if (d <= V::kInf) delta = d;  // (NaN bits lie above kInf: skipped)
         if (m <= V::kInf) xmax = m;
     }
-    changed = wave_max(changed);
-    delta = wave_max(delta);
-    xmax = wave_max(xmax);
-    __shared__ unsigned long long part[3][kThreads / kWave];
-    if (lane_id() == 0) {
-        part[0][wave_id()] = changed;
-        part[1][wave_id()] = delta;
-        part[2][wave_id()] = xmax;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long v = part[threadIdx.x][0];
-#pragma unroll
-        for (int w = 1; w < kThreads / kWave; w++) v = part[threadIdx.x][w] > v ? part[threadIdx.x][w] : v;
-        // a maximum only grows: a workgroup whose value the record already covers has nothing to add, and same-address atomics serialise
-        // at the memory side.  The look is a relaxed device-scope load; a value older than the record's is smaller, never larger.
-        unsigned long long *slot = threadIdx.x == 0 ? &mine->changed : (threadIdx.x == 1 ? &mine->delta : &mine->xmax);
-        if (v > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            if (threadIdx.x == 0) atomicOr(slot, 1ull);
-            else atomicMax(slot, v);
-        }
-    }
+    sweep_publish(changed, delta, xmax, mine);
 }
 
 struct SweepArgs {
@@ -157,16 +100,6 @@ void launch_variant(bool minor, bool lower, bool unit, bool stats, Args &&...arg
         if (lower) launch_stats<S, false, true>(unit, stats, args...);
         else launch_stats<S, false, false>(unit, stats, args...);
     }
-}
-
-int64_t check_from_env()
-{
-    if (const char *e = getenv("BMSP_SPITSV_CHECK")) {
-        char *end = nullptr;
-        const long long c = strtoll(e, &end, 10);
-        if (end != e && c >= 1) return (int64_t)c;
-    }
-    return kCheckDefault;
 }
 
 bool no_check(double tol) { return tol == BMSP_ITSV_NO_CHECK; }
@@ -236,7 +169,7 @@ void spitsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const vo
     if (!stats) {
         for (int64_t k = 0; k < m; k++) sweep(k, nullptr, nullptr);
     } else {
-        const int64_t check = check_from_env();
+        const int64_t check = sweep_check_from_env("BMSP_SPITSV_CHECK", kCheckDefault);
         DevBuf<SweepRecord> recs((size_t)m);
         std::vector<SweepRecord> host((size_t)m);
         BMSP_HIP(hipMemsetAsync(recs.p, 0, sizeof(SweepRecord) * (size_t)m, st));

@@ -29,6 +29,8 @@ FILL_LOWER, FILL_UPPER = 0, 1
 DIAG_NON_UNIT, DIAG_UNIT = 0, 1
 ITSV_X0_GIVEN = 1
 ITSV_NO_CHECK = -1.0
+ILU_F0_GIVEN = 1
+ILU_NO_CHECK = -1.0
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
@@ -43,7 +45,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -139,6 +141,16 @@ class SpitsvInfo(C.Structure):
         return d
 
 
+class Ilu0Info(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("sweeps", C.c_int64), ("max_sweeps", C.c_int64), ("converged", C.c_int),
+                ("delta", C.c_double), ("fmax", C.c_double), ("view_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
 class ShardStats(C.Structure):
     _fields_ = [("world", C.c_int), ("rank", C.c_int), ("panel_block_row_begin", C.c_int64), ("panel_block_row_end", C.c_int64),
                 ("panel_tasks", C.c_int64), ("exchange_bytes", C.c_int64), ("exchange_us", C.c_double), ("exchange_exposed_us", C.c_double),
@@ -217,6 +229,8 @@ def lib():
         L.bmsp_spsm.argtypes = [vp, i, i, i, C.c_double, vp, i64, vp, i64, i, vp]
         L.bmsp_spsm_launch_info.argtypes = [vp, i, i, i, i, i64, i64, vp, p(SpsmInfo)]
         L.bmsp_spitsv.argtypes = [vp, i, i, i, C.c_double, vp, vp, i64, C.c_double, i, vp, p(SpitsvInfo), vp]
+        L.bmsp_matrix_ilu0.argtypes = [vp, i64, C.c_double, i, vp, p(vp), vp, p(Ilu0Info)]
+        L.bmsp_matrix_ilu0_values.argtypes = [vp, vp, i64, C.c_double, i, vp, vp, p(Ilu0Info)]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -537,6 +551,10 @@ class BmSpMatrix:
         """block-Jacobi sweeps towards the x of op(tri(this)) * x = alpha * b: pybmsp.spitsv"""
         return spitsv(self, b, op, fill, unit_diag, alpha, max_iter, tol, x, x0_given, history, stream)
 
+    def ilu0(self, max_iter=0, tol=0.0, out_transposed=None, history=False, stream=None):
+        """(F, info[, history]): the incomplete factor ILU(0) of this matrix by fixed-point sweeps: pybmsp.ilu0"""
+        return ilu0(self, max_iter, tol, out_transposed, history, stream)
+
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
         return spgemm_masked(self, B, M, alpha, beta, mul_m, transposed, stream)
@@ -844,6 +862,47 @@ def spitsv(A, b, op="N", fill="lower", unit_diag=False, alpha=1.0, max_iter=0, t
                             ITSV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info), stream))
     d = info.as_dict()
     return (x, d, hist[:d["sweeps"]].copy()) if history else (x, d)
+
+
+def _ilu0_history(A, max_iter, history):
+    if not history:
+        return None
+    cap = int(max_iter) if max_iter else 2 * A.info()["num_rows"]
+    return np.zeros(max(cap, 1), np.float64)
+
+
+def ilu0(A, max_iter=0, tol=0.0, out_transposed=None, history=False, stream=None):
+    """The incomplete factorisation ILU(0) of A on its own pattern by fixed-point sweeps (bmsp_matrix_ilu0): F has A's structure in layout
+    `out_transposed` (None: A's) and holds L (unit diagonal, not stored) below the diagonal and U on and above it -- what
+    spsv(F, b, "N", "lower", True) followed by spsv(F, y, "N", "upper") applies.  A sweep is one launch that recomputes every stored entry
+    from the previous iterate, started from A's values; after 2n - 1 sweeps F holds the sequential ILU(0) bit for bit.  Stops after a
+    sweep that changed nothing or, with tol > 0, whose largest update is at most tol times the largest |f_ij|; max_iter=0 means 2n.
+    tol=ILU_NO_CHECK runs exactly max_iter sweeps, nothing read back (history must be False).  A needs every diagonal entry stored.
+    Returns (F, info) or (F, info, history): info = {"kernel", "lanes", "sweeps", "max_sweeps", "converged", "delta", "fmax",
+    "view_bytes"}, history = the delta of every sweep that ran (float64)."""
+    lay = A.info()["transposed"] if out_transposed is None else int(bool(out_transposed))
+    info = Ilu0Info()
+    hist = _ilu0_history(A, max_iter, history)
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_ilu0(A.h, int(max_iter), float(tol), lay, stream, C.byref(h), hist.ctypes.data if history else None,
+                                 C.byref(info)))
+    d = info.as_dict()
+    F = BmSpMatrix(h.value)
+    return (F, d, hist[:d["sweeps"]].copy()) if history else (F, d)
+
+
+def ilu0_values(A, F, max_iter=0, tol=0.0, history=False, stream=None, f0_given=False):
+    """the sweeps of ilu0(A, ...) into an existing F made from A by ilu0() / with_layout() / scale() / sddmm() / spgemm_masked(); never A
+    itself.  f0_given: start from F's current values, the warm start after a value-only update of A (default: from A's values, F is not
+    read).  Returns (F, info) or (F, info, history) (bmsp_matrix_ilu0_values)."""
+    if F is A or (F.h is not None and F.h == A.h):
+        raise ValueError("F must not be A: a is read in every sweep")
+    info = Ilu0Info()
+    hist = _ilu0_history(A, max_iter, history)
+    check(lib().bmsp_matrix_ilu0_values(A.h, F.h, int(max_iter), float(tol), ILU_F0_GIVEN if f0_given else 0, stream,
+                                        hist.ctypes.data if history else None, C.byref(info)))
+    d = info.as_dict()
+    return (F, d, hist[:d["sweeps"]].copy()) if history else (F, d)
 
 
 def _spsm_strides(k, ldb, ldx):

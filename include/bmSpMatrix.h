@@ -329,6 +329,30 @@ inline void bmSparse_SpITSV(bmSpMatrix<ValueIn> &A, int op, int fill, int diag, 
     bmsp::check(bmsp_synchronize());
 }
 
+/* Incomplete factorisation ILU(0) by fixed-point sweeps (bmsp_matrix_ilu0 / bmsp_matrix_ilu0_values): F receives A's structure in the
+ * layout asked for and holds L (unit diagonal, not stored) below the diagonal and U on and above it -- what bmSparse_SpSV(F, N, LOWER,
+ * UNIT) followed by bmSparse_SpSV(F, N, UPPER, NON_UNIT) applies.  A must be square with every diagonal entry stored.  max_iter == 0
+ * means 2 n (then tol == 0 returns the sequential ILU(0)'s bits); tol > 0 stops at max |f_new - f_old| <= tol * max |f_new|; tol ==
+ * BMSP_ILU_NO_CHECK runs exactly max_iter sweeps with nothing read back.  The _values form writes into an F made from A by bmSparse_ILU0
+ * or a layout-keeping maker, never into A; flags: BMSP_ILU_F0_GIVEN = start from F's current values (default: from A's).  delta_history
+ * (host) and info may be null; synchronous like bmSparse_SpMV. */
+template <class ValueIn>
+inline void bmSparse_ILU0(bmSpMatrix<ValueIn> &A, bmSpMatrix<ValueIn> &F, int64_t max_iter = 0, double tol = 0.0, bool transposed_layout = false,
+                          double *delta_history = nullptr, bmsp_ilu0_info *info = nullptr)
+{
+    bmsp_matrix_t f = nullptr;
+    bmsp::check(bmsp_matrix_ilu0(A.handle(), max_iter, tol, transposed_layout ? 1 : 0, nullptr, &f, delta_history, info));
+    bmsp::check(bmsp_synchronize());
+    F.reset(f);
+}
+template <class ValueIn>
+inline void bmSparse_ILU0_values(bmSpMatrix<ValueIn> &A, bmSpMatrix<ValueIn> &F, int64_t max_iter = 0, double tol = 0.0, int flags = 0,
+                                 double *delta_history = nullptr, bmsp_ilu0_info *info = nullptr)
+{
+    bmsp::check(bmsp_matrix_ilu0_values(A.handle(), F.handle(), max_iter, tol, flags, nullptr, delta_history, info));
+    bmsp::check(bmsp_synchronize());
+}
+
 /* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are
  * device pointers to num_rows x k row-major arrays at leading dimensions ldb, ldx >= k (float, double for double); they may be the same
  * when ldb == ldx.  Column c of X holds the bits bmSparse_SpSV writes for column c of B, for one walk of the dependency chain instead of

@@ -523,6 +523,79 @@ int bmsp_spitsv(bmsp_matrix_t A, int op, int fill, int diag, double alpha, const
                 int64_t max_iter, double tol, int flags, double *delta_history /* host, may be NULL */,
                 bmsp_spitsv_info *info /* may be NULL */, void *stream);
 
+/* ILU(0), the incomplete factorisation on A's own pattern, by the fixed-point sweeps of Chow and Patel (SIAM J. Sci. Comput. 37, 2015):
+ * the factor that bmsp_spsv / bmsp_spsm / bmsp_spitsv apply, made on the device without a host round trip.  It is to a level-scheduled
+ * exact factorisation what bmsp_spitsv is to bmsp_spsv: a sweep is ONE launch in which every stored entry is recomputed independently from
+ * the previous iterate -- no level schedule, no dependency chain, nothing waits between workgroups, every value has exactly one writer.
+ * Nothing in the reference is replaced (it has no factorisation).
+ *   Operands: A is n x n with every diagonal entry (i, i), i < n, stored; F32, F16 or F64; either tile layout.  S = the set of A's stored
+ *       coordinates.  F has A's shape, dtype and structure and holds both factors: L (unit diagonal, not stored) in the strict lower
+ *       triangle, U in the upper triangle including the diagonal -- exactly what bmsp_spsv(F, N, LOWER, UNIT) followed by bmsp_spsv(F, N,
+ *       UPPER, NON_UNIT) applies.  Arithmetic is fp32 for F32 and F16 (F16 values are widened exactly), double for F64.
+ *   A sweep computes F^{k+1} from F^k for EVERY (i, j) of S:
+ *           s = a_ij
+ *           for k ascending over k < min(i, j) with (i, k) in S and (k, j) in S:   s = fma(-f^k_ik, f^k_kj, s)
+ *           if i > j:  s = s / f^k_jj          (one IEEE division, the full sequence, never a reciprocal)
+ *           f^{k+1}_ij = s rounded once to the storage type (F16: round-to-nearest-even, may overflow)
+ *       All reads come from the previous iterate; F^0 = A's values, or F's current values under BMSP_ILU_F0_GIVEN.  Unstored positions
+ *       never contribute, a stored 0 does.  Subnormals are kept.  A zero pivot gives what IEEE gives; Inf and NaN travel along
+ *       dependencies only.  The arithmetic of a sweep is fixed bit for bit.
+ *   Finite termination: entry (i, j) with m = min(i, j) holds its final bits after sweep 2m + 1 when i <= j and after sweep 2m + 2 when
+ *       i > j (induction over m: its operands are entries with a smaller min, the diagonal (j, j) included).  So after 2n - 1 sweeps F is
+ *       bit for bit the sequential ILU(0) that evaluates the same chain row by row, columns ascending, in place -- the only bitwise fixed
+ *       point of the sweep.  max_iter == 0 means 2n.
+ *   Per-sweep statistics, order-independent and therefore deterministic (as bmsp_spitsv's): changed = some entry differs in bits from the
+ *       previous iterate; delta = max |fl(f^{k+1} - f^k)| and fmax = max |f^{k+1}|, both in the arithmetic type, NaNs skipped.
+ *   Stop rule, in the arithmetic type with tol rounded once: stop after sweep k iff !changed || (tol > 0 && delta <= fl(tol * fmax)).
+ *       tol == 0 means "until nothing changes".  F, sweeps and converged are a pure function of A's arrays, F^0, tol and max_iter: they
+ *       do not depend on the stream, on BMSP_ILU0_LANES or on BMSP_ILU0_CHECK.  An iterate that holds an Inf has delta = fmax = Inf,
+ *       which meets the rule under any tol > 0: a caller who stops by tolerance checks that info->delta is finite (where the iteration
+ *       does not contract, iterates may grow before finite termination brings the factor back; the call does not detect it).
+ *   tol == BMSP_ILU_NO_CHECK, the preconditioner mode (three to five sweeps): exactly max_iter sweeps (2n for 0) by a kernel instantiation
+ *       without statistics; nothing is read back and, once F's buffers exist, the call is asynchronous on `stream`.  delta_history must
+ *       be NULL; info gets sweeps = max_iter, converged = 0 and delta = fmax = -1.
+ *   bmsp_matrix_ilu0: *F is a fresh pool-owned matrix of A's structure with tiles in layout out_transposed; its keys, bitmaps, offsets
+ *       and block-row pointer equal bmsp_matrix_convert_layout(A, out_transposed)'s, and it remembers A the way a bmsp_matrix_scale or
+ *       bmsp_spgemm_masked output does.  Making it synchronises `stream`.
+ *   bmsp_matrix_ilu0_values: the same sweeps into an existing F, which must have been made from A by bmsp_matrix_ilu0 or by one of the
+ *       layout-keeping makers (bmsp_matrix_convert_layout, bmsp_matrix_scale, bmsp_sddmm, bmsp_spgemm_masked) while A's STRUCTURE has not
+ *       changed since (the rule of bmsp_spgemm_masked_values); F == A is refused, a is read in every sweep.  With BMSP_ILU_F0_GIVEN the
+ *       sweeps start from F's current values: the warm start after a value-only update of A, which needs no bmsp_matrix_invalidate.
+ *       Without the flag F's values are not read -- whatever they held, NaN included, never reaches the result.  Drops F's value-derived
+ *       caches before writing, as bmsp_spgemm_masked_values does.
+ *   A, its four arrays and its caches are never modified.
+ *   Results: delta_history (host, may be NULL): delta_history[k], k < sweeps, = sweep k's delta, widened exactly.  info (may be NULL):
+ *       the kernel instantiation by name ("ilu0_sweep_kernel<F32, 8, STATS>": dtype, lanes per tile, STATS / NO_STATS; "none (empty
+ *       matrix)"), the lanes per tile, sweeps = the sweeps that ran, max_sweeps = the cap that applied, converged = the stop rule held at
+ *       sweep `sweeps`, the last sweep's delta and fmax, and view_bytes = the bytes of F's op-T view plus its diagonal index.
+ *   Kernel (vector ALU): ilu0_sweep_kernel, modelled on spgemm_masked_kernel.  1 or 8 lanes per tile (BMSP_ILU0_LANES=1/8, read per call;
+ *       default eight at every fill, the measured choice of the masked product).  A lane owns one byte of the output bitmap with eight
+ *       accumulators in registers, started from a_ij.  It walks block-row I of F through F's block-row pointer and block-column J of F
+ *       through the cached op-T view of bmsp_spmv_op(F, BMSP_OP_T) (structure only, keyed to F, dropped by the usual events) in ascending
+ *       K, stops at K > min(I, J), and in a pair with K == min(I, J) cuts the common-index mask to k < min(i, j) per output position.
+ *       Either layout of A and of F is read through the transposed bitmap; the tile order is the same in both.  f^k_jj is read through
+ *       a per-structure array of the value index of every (j, j): n 32-bit entries, built once on the device when F's buffers are made
+ *       -- that is where a missing diagonal is found --, kept on F's handle, freed and invalidated with the view.  A hub x hub tile
+ *       (both lists long, a power-law matrix) is one lane group's serial chain, as in the masked product; it is not split.
+ *   Buffers: the iterates ping-pong between F's value array and ONE temporary of nnz storage elements kept on F's handle; the last
+ *       iterate ends in F's value array, with at most one asynchronous device copy.  Because of that temporary, calls on one F must not
+ *       overlap on different streams.
+ *   Statistics and stopping are bmsp_spitsv's protocol: wave and LDS reduction, at most one integer atomic max / or per workgroup and
+ *       statistic into the sweep's own record (no floating-point atomic); sweep k + 1 evaluates the stop rule on record k and returns
+ *       without writing if it holds; the host enqueues BMSP_ILU0_CHECK=<sweeps> sweeps (read per call, default 8) between read-backs.
+ *   n == 0 or a matrix without tiles: a valid empty F, sweeps = 0, kernel "none (empty matrix)".
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing done on the device: max_iter < 0 or
+ *   > 2^20; tol NaN, or negative and not BMSP_ILU_NO_CHECK; out_transposed not 0 / 1; flags with unknown bits; delta_history given under
+ *   BMSP_ILU_NO_CHECK; null A, F or out pointer; a non-square A; row-panel views; F not made from A, or F == A; a row whose diagonal
+ *   entry is not stored (the message names the first such row, as bmsp_spsv's does).  BMSP_ERR_LIMIT: 2^32 tiles or values or more. */
+#define BMSP_ILU_F0_GIVEN 1
+#define BMSP_ILU_NO_CHECK (-1.0)
+typedef struct { char kernel[64]; int lanes; int64_t sweeps, max_sweeps; int converged; double delta, fmax; int64_t view_bytes; } bmsp_ilu0_info;
+int bmsp_matrix_ilu0(bmsp_matrix_t A, int64_t max_iter, double tol, int out_transposed, void *stream,
+                     bmsp_matrix_t *F, double *delta_history, bmsp_ilu0_info *info);
+int bmsp_matrix_ilu0_values(bmsp_matrix_t A, bmsp_matrix_t F, int64_t max_iter, double tol, int flags, void *stream,
+                            double *delta_history, bmsp_ilu0_info *info);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
