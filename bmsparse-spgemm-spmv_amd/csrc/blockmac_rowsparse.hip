@@ -337,7 +337,7 @@ void ensure_csr32(bmsp_matrix_s *m, hipStream_t st)
 // tile-by-tile kernel multiplies.  Needs finite values and, for fp32, every product of stored values a normal number (biased exponents
 // summing to >= 128); the caller bounds the block-rows of C by mac_strip_row_cap() tiles.  BMSP_MAC_ROWSPARSE=0/1: never / whatever
 // the fill.
-bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values)
+bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st)
 {
     const char *e = getenv("BMSP_MAC_ROWSPARSE");
     if (e && e[0] == '0') return false;
@@ -345,7 +345,6 @@ bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, h
     if ((uint64_t)A->nnz >= (1ull << 29) || (uint64_t)B->nnz >= (1ull << 29)) return false;  // (8-byte entries behind 32-bit byte offsets)
     if (A->view_values_end || B->view_values_end || A->ownership == 2 || B->ownership == 2) return false;  // (row-panel views: no copy of their own)
     if (!(e && e[0] == '1') && !(A->nnz <= 16 * A->block_num && B->nnz <= 16 * B->block_num)) return false;
-    if (ignore_values) return true;
     ensure_finite_flag(A, st);
     ensure_finite_flag(B, st);
     if (A->values_finite != 1 || B->values_finite != 1) return false;

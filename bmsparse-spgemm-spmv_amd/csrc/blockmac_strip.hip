@@ -589,7 +589,7 @@ void ensure_finite_flag(bmsp_matrix_s *m, hipStream_t st)
 
 // what the strip kernel needs of the operands alone: fp16 tiles the K = 32 MFMA path addresses, a strip's merged A tiles within the k
 // list, finite values (cached per-matrix figures; the read-backs behind them happen once per matrix)
-bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st, bool ignore_values)
+bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st)
 {
     if (A->dtype == BMSP_F16) {
         if (!mac_mfma32_supported(A, B)) return false;
@@ -598,18 +598,15 @@ bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st, b
         if (B->dtype != BMSP_F32 || A->block_num >= (1ll << 24) || B->block_num >= (1ll << 24) || !mac_f32_mfma_usable(st)) return false;
         // every product a normal number (|a| |b| >= 2^(ea + eb - 254) >= 2^-126) and every sum far from overflow: outside that range the
         // matrix pipe's rounding is not the fmaf chain's, and V15's vector-ALU kernel (task-list mode or the pipeline) takes the product
-        if (!ignore_values) {
-            ensure_finite_flag(A, st);
-            ensure_finite_flag(B, st);
-            if (A->f32_exp_min + B->f32_exp_min < mac_f32_exp_floor(st) || A->f32_exp_max + B->f32_exp_max > 254 + 100) return false;
-        }
+        ensure_finite_flag(A, st);
+        ensure_finite_flag(B, st);
+        if (A->f32_exp_min + B->f32_exp_min < mac_f32_exp_floor(st) || A->f32_exp_max + B->f32_exp_max > 254 + 100) return false;
     } else {
         return false;
     }
     if ((uint64_t)A->num_block_rows() >= (1ull << 31)) return false;
     ensure_row_stats(A, st);
     if (2 * A->max_row_blocks > kKCap) return false;
-    if (ignore_values) return true;
     ensure_finite_flag(A, st);
     ensure_finite_flag(B, st);
     return A->values_finite == 1 && B->values_finite == 1;
@@ -640,11 +637,11 @@ bool mac_strip_eligible(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, ui
 }
 
 // the numeric stages that need no task list: the row-sparse kernel (V15 numerics on nearly empty tiles) or the strip kernels
-bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values)
+bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st)
 {
-    if (mac_rowsparse_applies(A, B, tc_version, st, ignore_values)) return true;
+    if (mac_rowsparse_applies(A, B, tc_version, st)) return true;
     if (A->dtype == BMSP_F16 && tc_version != 4) return false;  // the fp16 strip kernel has the matrix cores' numerics
-    return mac_strip_operands_ok(A, B, st, ignore_values);
+    return mac_strip_operands_ok(A, B, st);
 }
 
 int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st)

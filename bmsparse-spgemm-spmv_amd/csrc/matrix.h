@@ -80,10 +80,14 @@ struct bmsp_matrix_s {
     void *dense_tiles = nullptr;
     uint32_t *csr_rowptr = nullptr, *csr_ent = nullptr;  // fp32 operands of the row-sparse block-MAC: a row-major CSR copy (row pointer of num_rows + 1 entries; {column, value bits} per stored value)
     void *lane_tiles = nullptr;   // fp32 matrices: tiles in the lane order of the fp32 MFMA block-MAC (256 B per block): built lazily
-    // SpGEMM row-merge paths: the right operand (keys pointer, block count) this matrix was last multiplied with and what that product
-    // turned out to need (1 strip mode, 2 task-list mode, 3 the pipeline, 4 column windows) -- the next product of the pair goes there directly
+    // SpGEMM row-merge paths: what the product of this matrix with the right operand whose uid is rm_partner_uid (B's uid: the key of the
+    // three fields below) turned out to need, so that the next product of the pair goes there directly.  The memory holds only what the
+    // pair's STRUCTURE needs, two facts kept apart: whether strip mode fits (rm_partner_strip: 0 unknown, 1 a strip pass ran and fitted,
+    // 2 a strip pass ran and a block-row of C did not fit) and which path forms the task list otherwise (rm_partner_mode: 0 unknown,
+    // 2 task-list mode, 3 the pipeline, 4 column windows).  A call whose arguments, switches or operand values keep strip mode out, or
+    // whose left operand is refused for being a row-panel view, runs no strip pass and writes nothing about strip mode.
     uint64_t rm_partner_uid = 0;
-    int64_t rm_partner_blocks = 0;
+    int rm_partner_strip = 0;
     int rm_partner_mode = 0;
     int64_t rm_partner_cw_hash = 0;  // column-window passes: candidate pairs per hashed window that worked for the pair (0: the default)
     // a product made by bmsp_spgemm_symbolic keeps its sorted task list for bmsp_spgemm_numeric (T_7 alone on new operand values)
@@ -148,19 +152,30 @@ struct bmsp_comm_s {
 
 namespace bmsp {
 
-// A row-panel view inherits what its parent learned about a right operand (which row-merge mode the pair needs) and hands back what it
-// learned itself: views are made per call, and without this every panel product would pay for a pass that does not fit (hub block-rows).
+// What `m` remembers is about the right operand of uid `partner` from here on: a memory kept for another partner is not this pair's.
+inline void rm_hint_key(bmsp_matrix_s *m, uint64_t partner)
+{
+    if (m->rm_partner_uid == partner) return;
+    m->rm_partner_uid = partner; m->rm_partner_strip = 0; m->rm_partner_mode = 0; m->rm_partner_cw_hash = 0;
+}
+// A row-panel view inherits what its parent learned about a right operand and hands back what it learned itself: views are made per call,
+// and without this every panel product would pay for a pass that does not fit (hub block-rows).  What comes back holds for the parent:
+// a strip pass that overflowed on a panel overflows on every matrix that holds the panel's block-rows (2 stays), a panel that fitted
+// says so until another panel or the parent's own pass says otherwise, and of the list paths the one that corrects itself wins (a pair
+// sent to the column windows that does not need them ends in the pipeline and remembers that; the reverse never happens).  A view that
+// ran no strip pass -- the predicates refuse views where they accept the parent (mac_rowsparse_applies) -- has written nothing about
+// strip mode, so nothing of the kind reaches the parent.
 inline void rm_hint_inherit(bmsp_matrix_s *view, const bmsp_matrix_s *parent)
 {
-    view->rm_partner_uid = parent->rm_partner_uid; view->rm_partner_blocks = parent->rm_partner_blocks; view->rm_partner_mode = parent->rm_partner_mode;
+    view->rm_partner_uid = parent->rm_partner_uid; view->rm_partner_strip = parent->rm_partner_strip; view->rm_partner_mode = parent->rm_partner_mode;
     view->rm_partner_cw_hash = parent->rm_partner_cw_hash;
 }
 inline void rm_hint_merge(bmsp_matrix_s *parent, const bmsp_matrix_s *view)
 {
     if (!view->rm_partner_uid) return;
-    const bool same = parent->rm_partner_uid == view->rm_partner_uid;
-    const int mode = same && parent->rm_partner_mode > view->rm_partner_mode ? parent->rm_partner_mode : view->rm_partner_mode;
-    parent->rm_partner_uid = view->rm_partner_uid; parent->rm_partner_blocks = view->rm_partner_blocks; parent->rm_partner_mode = mode;
+    rm_hint_key(parent, view->rm_partner_uid);
+    if (view->rm_partner_strip == 2 || (view->rm_partner_strip == 1 && parent->rm_partner_strip == 0)) parent->rm_partner_strip = view->rm_partner_strip;
+    if (view->rm_partner_mode > parent->rm_partner_mode) parent->rm_partner_mode = view->rm_partner_mode;
     if (view->rm_partner_cw_hash) parent->rm_partner_cw_hash = view->rm_partner_cw_hash;
 }
 
@@ -204,14 +219,13 @@ int mac_f32_exp_floor(hipStream_t st);
 bool launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
                          bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
 bool mac_strip_eligible(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, uint64_t candidates, uint64_t n_tasks, hipStream_t st);
-// ignore_values: the answer as if both operands held ordinary finite values -- the structural half of the predicate alone
-bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st, bool ignore_values = false);
+bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st);
 bool mac_strip_fits_c(bmsp_matrix_s *C, hipStream_t st);
 uint32_t mac_strip_row_cap();
 int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st);  // returns the BMSP_MAC_* variant that ran (strip, or row-sparse for V15 numerics on nearly empty tiles)
-bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values = false);  // a numeric stage that works from C's structure alone exists for these operands
+bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);  // a numeric stage that works from C's structure alone exists for these operands
 void ensure_csr32(bmsp_matrix_s *m, hipStream_t st);
-bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st, bool ignore_values = false);
+bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);
 void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
 bool mac_rowsparse_fits_c(bmsp_matrix_s *C, hipStream_t st);  // every block-row of C within the row-sparse kernel's table (768 tiles)
 bool rowmerge_symbolic(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const uint64_t *first_pos, uint64_t total, uint32_t row_cap,

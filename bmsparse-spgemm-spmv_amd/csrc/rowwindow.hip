@@ -727,8 +727,8 @@ bool rowmerge_windowed(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, con
         if (getenv("BMSP_WIN_DEBUG")) fprintf(stderr, "[win] a hashed window overflowed\n");
         if (attempt == 3 || P.cw_hash <= 64u) return false;
         P.cw_hash /= 2;
-        if (A->rm_partner_uid != B->uid) A->rm_partner_mode = 0;  // (a mode remembered for another partner is not this pair's)
-        A->rm_partner_uid = B->uid; A->rm_partner_blocks = B->block_num; A->rm_partner_cw_hash = (int64_t)P.cw_hash;
+        rm_hint_key(A, B->uid);  // (what was remembered for another partner is not this pair's)
+        A->rm_partner_cw_hash = (int64_t)P.cw_hash;
     }
     DevBuf<uint32_t> tile_base((size_t)U + 1), task_base((size_t)U + 1);
     DevBuf<uint64_t> val_base((size_t)U + 1);

@@ -1070,6 +1070,11 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
     // of up to ~900 tiles; (3) the pipeline below otherwise (hub rows).  What a pair of operands turned out to need is remembered on A's
     // handle, so that only the first product of a pair pays for a pass that did not fit (cage-like: 280 us).  BMSP_SPGEMM_ROWMERGE=0
     // switches both off, =1 takes them under an explicit sort mode too, =2 skips strip mode.
+    // The memory records what the pair's STRUCTURE needs and nothing else (matrix.h, rm_partner_*): "strip mode does not fit" is written
+    // only by a strip pass that ran and overflowed, "it fits" only by one that ran and fitted; the list path (task-list mode, column
+    // windows, pipeline) is remembered beside it, not instead of it.  A product kept off strip mode by its arguments (the tc_version, a
+    // switch), by what the operands hold (values change) or by the predicates' refusal of a row-panel view says nothing about the pair:
+    // it neither replaces a remembered fit nor stands in for one -- the pair would stay off strip mode until a structure invalidate.
     uint64_t n_tasks = 0;
     uint32_t c_size = 0;
     DevBuf<uint64_t> k0, k1, v0, v1, rm_tasks;
@@ -1080,11 +1085,10 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         const char *rme = getenv("BMSP_SPGEMM_ROWMERGE");
         const bool rm_force = rme && rme[0] != '0', rm_off = rme && rme[0] == '0', rm_no_strip = rme && rme[0] == '2';
         const bool known = A->rm_partner_uid == B->uid;
-        const int hint = known ? A->rm_partner_mode : 0;  // 0 unknown, 1 strip mode fits, 2 task-list mode, 3 pipeline
-        auto remember = [&](int m) {
-            if (A->rm_partner_uid != B->uid) A->rm_partner_cw_hash = 0;
-            A->rm_partner_uid = B->uid; A->rm_partner_blocks = B->block_num; A->rm_partner_mode = m;
-        };
+        const int strip_fit = known ? A->rm_partner_strip : 0;  // 0 unknown, 1 strip mode fits, 2 a strip pass ran and did not fit
+        const int hint = known ? A->rm_partner_mode : 0;        // the list path otherwise: 0 unknown, 2 task-list mode, 3 pipeline, 4 column windows
+        auto remember_strip = [&](int fit) { rm_hint_key(A, B->uid); A->rm_partner_strip = fit; };
+        auto remember_list = [&](int m) { rm_hint_key(A, B->uid); A->rm_partner_mode = m; };
         // numeric stages that work from C's structure alone: the K = 32 MFMA strip kernel (tc_version 4, fp16) and its fp32 form (V15's
         // summation order on v_mfma_f32_16x16x4_f32: any tc_version, as fp32 operands always take V15's numerics)
         // ... and the row-sparse kernel: V15 numerics (fp32 operands, or fp16 under tc_version 5 -- the reference's default configuration) on
@@ -1099,7 +1103,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         // strip mode done: value array, numeric stage (or zero values for bmsp_spgemm_symbolic), statistics
         auto finish_strip = [&](uint64_t surv) {
             tm.mark(3);
-            remember(1);
+            remember_strip(1);
             S->task_list_size = (int64_t)total;
             S->surviving_tasks = (int64_t)surv;
             S->bmp_reduction = (int64_t)(total - surv);
@@ -1127,7 +1131,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         // (also for a pair never seen whose row maxima bound every block-row of C by the strip kernel's capacity)
         const bool surely_fits = A->max_row_blocks >= 0 && B->max_row_blocks >= 0 &&
                                  (uint64_t)A->max_row_blocks * (uint64_t)B->max_row_blocks <= (uint64_t)mac_strip_row_cap();
-        if (((known && hint == 1) || (hint == 0 && surely_fits)) && n_a && strip_allowed && (mode == BMSP_SORT_AUTO || rm_force) && !rm_off &&
+        if ((strip_fit == 1 || (strip_fit == 0 && surely_fits)) && n_a && strip_allowed && (mode == BMSP_SORT_AUTO || rm_force) && !rm_off &&
             (uint64_t)A->num_block_rows() * (uint64_t)mac_strip_row_cap() * 12 <= (4ull << 30) &&  // (beyond: T_2 first, scratch sized by the candidate pairs)
             mac_structure_numeric_ok(A, B, tc_version, st)) {
             uint64_t surv = 0;
@@ -1139,21 +1143,18 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
                 }
                 drop_structure();
             }
+            remember_strip(2);  // the pass ran and a block-row (or a strip) of C did not fit: the next product does not try it again
             tm.mark(-1);
         }
         run_t2();
         const bool rm_on = !rm_off && total && (mode == BMSP_SORT_AUTO || rm_force);
-        bool try_strip = rm_on && strip_allowed && !strip_tried && hint != 2 && hint != 3 && hint != 4;
-        // strip mode left out ONLY because of what the operands hold (the cached value figures: non-finite values, fp32 exponents outside
-        // the matrix pipe's range -- the structural half of the predicate accepts the pair): the mode that runs instead says nothing about
-        // what the pair's structure needs, and values change (bmsp_matrix_invalidate(m, 0), copy / add / scale / sddmm into a handle) --
-        // it is not remembered, or the pair would stay off strip mode for good.  A structural refusal (hub block-rows, tile fill, views)
-        // is remembered as before: only the first product of such a pair pays for a pass that does not fit.
-        bool strip_refused_by_values = false;
-        if (try_strip) {
-            try_strip = mac_structure_numeric_ok(A, B, tc_version, st);
-            strip_refused_by_values = !try_strip && mac_structure_numeric_ok(A, B, tc_version, st, true);
-        }
+        // Strip mode is tried unless a pass is known to have overflowed.  Where the predicate refuses -- what the operands hold (the cached
+        // value figures: non-finite values, fp32 exponents outside the matrix pipe's range; values change: bmsp_matrix_invalidate(m, 0),
+        // copy / add / scale / sddmm into a handle), the tile fill under this tc_version, a row-panel view -- no pass runs and nothing is
+        // written about strip mode: the predicate costs a few comparisons of cached figures and is asked again by the next product, while
+        // a remembered refusal would keep the pair off strip mode for good.  Only a pass that ran and did not fit is remembered (hub
+        // block-rows): the first product of such a pair alone pays for it.
+        bool try_strip = rm_on && strip_allowed && !strip_tried && strip_fit != 2 && mac_structure_numeric_ok(A, B, tc_version, st);
         if (try_strip) {
             uint64_t surv = 0, cand = 0;
             if (rowmerge_symbolic(A, B, C.get(), first_pos.p, total, mac_strip_row_cap(), &surv, &cand, st)) {
@@ -1164,6 +1165,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
                 // C exists but a strip of it exceeds the kernel's column list: drop it
                 drop_structure();
             }
+            remember_strip(2);
             tm.mark(-1);
         }
         if (rm_on && hint != 3) {
@@ -1173,8 +1175,10 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
             const bool tasklist_tried = hint != 4 && !win_force;
             if (hint != 4 && !win_force && rowmerge_tasklist(A, B, C.get(), first_pos.p, total, rm_tasks, task_begin, c_of_wave, &n_tasks, st)) got = 2;
             else if (!win_off && rowmerge_windowed(A, B, C.get(), first_pos.p, total, rm_tasks, task_begin, c_of_wave, &n_tasks, st)) got = 4;
+            // (the test switches decide here as well: column windows forced where task-list mode would do, or switched off where they
+            // would -- neither is what the pair needs, neither is remembered)
             if (got) {
-                if (!strip_refused_by_values) remember(got);
+                if (got == 2 || !win_force) remember_list(got);
                 have_tasks = true;
                 tasks_sorted = rm_tasks.p;
                 c_size = (uint32_t)C->block_num;
@@ -1187,7 +1191,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
                 finish_structure();
                 tm.mark(9);
             } else {
-                remember(3);
+                if (!win_off && !win_force) remember_list(3);
                 tm.mark(-1);
             }
         }
