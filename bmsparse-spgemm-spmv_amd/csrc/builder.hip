@@ -422,6 +422,7 @@ void drop_spmv_op_views(bmsp_matrix_s *m)
     pool_free(m->spmm_op_tmp); m->spmm_op_tmp = nullptr; m->spmm_op_tmp_elems = 0;
     pool_free(m->ilu0_diag); m->ilu0_diag = nullptr; m->ilu0_missing_row = -2;
     pool_free(m->ilu0_tmp); m->ilu0_tmp = nullptr;
+    pool_free(m->krylov_ws); m->krylov_ws = nullptr; m->krylov_ws_bytes = 0;
 }
 
 void alloc_tile_arrays(bmsp_matrix_s *m, uint64_t nb)

@@ -773,6 +773,37 @@ int bmsp_matrix_ilu0_values(bmsp_matrix_t A, bmsp_matrix_t F, int64_t max_iter, 
     BMSP_API_END
 }
 
+int bmsp_vec_dot(int64_t n, int vec_f64, const void *d_x, const void *d_y, double *d_result, void *stream)
+{
+    BMSP_API_BEGIN
+    vec_check_args(n, vec_f64);
+    need(d_result, "d_result");
+    load_kernels();
+    vec_dot(n, vec_f64, d_x, d_y, d_result, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_vec_axpby(int64_t n, int vec_f64, double a, const void *d_x, double b, void *d_y, void *stream)
+{
+    BMSP_API_BEGIN
+    vec_check_args(n, vec_f64);
+    load_kernels();
+    vec_axpby(n, vec_f64, a, d_x, b, d_y, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *pc, const void *d_b, void *d_x, int64_t max_iter, double tol,
+                      int flags, double *relres_history, bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    krylov_check_args(op, method, pc, max_iter, tol, flags, relres_history);
+    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
+    krylov_check_operands(A, pc, d_b, d_x);
+    load_kernels();
+    krylov_solve(A, op, method, pc, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                    uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
 {

@@ -128,6 +128,10 @@ struct bmsp_matrix_s {
     uint32_t *ilu0_diag = nullptr;
     int64_t ilu0_missing_row = -2;
     void *ilu0_tmp = nullptr;
+    // bmsp_krylov_solve (krylov.hip), on A: one allocation -- scalars and ticket | dot partials | diagonal | vectors | records -- sized
+    // for the largest need seen; goes with the views (drop_spmv_op_views); one stream per handle at a time
+    void *krylov_ws = nullptr;
+    size_t krylov_ws_bytes = 0;
     // a row-panel view points into its parent
     int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
@@ -336,6 +340,15 @@ bmsp_matrix_s *ilu0_matrix(bmsp_matrix_s *A, int64_t max_iter, double tol, int o
                            bmsp_ilu0_info *info);
 void ilu0_values_into(bmsp_matrix_s *A, bmsp_matrix_s *F, int64_t max_iter, double tol, int flags, hipStream_t st, double *delta_history,
                       bmsp_ilu0_info *info);
+// krylov.hip: the deterministic dot product and the scaled sum of device vectors; CG and BiCGStab for op(A) x = b with the iteration
+// enqueued on `st` (scalars, status and records device-resident)
+void vec_check_args(int64_t n, int vec_f64);
+void vec_dot(int64_t n, int vec_f64, const void *x, const void *y, double *result, hipStream_t st);
+void vec_axpby(int64_t n, int vec_f64, double a, const void *x, double b, void *y, hipStream_t st);
+void krylov_check_args(int op, int method, const bmsp_precond *pc, int64_t max_iter, double tol, int flags, const double *relres_history);
+void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc, const void *b, const void *x);
+void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const void *b, void *x, int64_t max_iter, double tol,
+                  int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

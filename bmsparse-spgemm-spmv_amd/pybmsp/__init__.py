@@ -31,6 +31,12 @@ ITSV_X0_GIVEN = 1
 ITSV_NO_CHECK = -1.0
 ILU_F0_GIVEN = 1
 ILU_NO_CHECK = -1.0
+KRYLOV_CG, KRYLOV_BICGSTAB = 0, 1
+PC_NONE, PC_JACOBI, PC_ILU_EXACT, PC_ILU_SWEEPS = 0, 1, 2, 3
+KRYLOV_X0_GIVEN = 1
+KRYLOV_NO_CHECK = -1.0
+KRYLOV_MAXITER, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN = 0, 1, 2
+_METHODS = {"cg": KRYLOV_CG, "bicgstab": KRYLOV_BICGSTAB, KRYLOV_CG: KRYLOV_CG, KRYLOV_BICGSTAB: KRYLOV_BICGSTAB}
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
@@ -45,7 +51,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -151,6 +157,21 @@ class Ilu0Info(C.Structure):
         return d
 
 
+class Precond(C.Structure):
+    _fields_ = [("kind", C.c_int), ("F", C.c_void_p), ("sweeps", C.c_int64)]
+
+
+class KrylovInfo(C.Structure):
+    _fields_ = [("method", C.c_char * 32), ("iterations", C.c_int64), ("max_iterations", C.c_int64), ("status", C.c_int),
+                ("relres", C.c_double), ("bnorm", C.c_double), ("products", C.c_int64), ("precond_applies", C.c_int64),
+                ("workspace_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["method"] = self.method.decode()
+        return d
+
+
 class ShardStats(C.Structure):
     _fields_ = [("world", C.c_int), ("rank", C.c_int), ("panel_block_row_begin", C.c_int64), ("panel_block_row_end", C.c_int64),
                 ("panel_tasks", C.c_int64), ("exchange_bytes", C.c_int64), ("exchange_us", C.c_double), ("exchange_exposed_us", C.c_double),
@@ -231,6 +252,9 @@ def lib():
         L.bmsp_spitsv.argtypes = [vp, i, i, i, C.c_double, vp, vp, i64, C.c_double, i, vp, p(SpitsvInfo), vp]
         L.bmsp_matrix_ilu0.argtypes = [vp, i64, C.c_double, i, vp, p(vp), vp, p(Ilu0Info)]
         L.bmsp_matrix_ilu0_values.argtypes = [vp, vp, i64, C.c_double, i, vp, vp, p(Ilu0Info)]
+        L.bmsp_vec_dot.argtypes = [i64, i, vp, vp, vp, vp]
+        L.bmsp_vec_axpby.argtypes = [i64, i, C.c_double, vp, C.c_double, vp, vp]
+        L.bmsp_krylov_solve.argtypes = [vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -554,6 +578,10 @@ class BmSpMatrix:
     def ilu0(self, max_iter=0, tol=0.0, out_transposed=None, history=False, stream=None):
         """(F, info[, history]): the incomplete factor ILU(0) of this matrix by fixed-point sweeps: pybmsp.ilu0"""
         return ilu0(self, max_iter, tol, out_transposed, history, stream)
+
+    def solve(self, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+        """(x, info[, history]) with op(this) * x = b by CG or BiCGStab on the device: pybmsp.krylov_solve"""
+        return krylov_solve(self, b, method, precond, op, max_iter, tol, x, x0_given, history, stream)
 
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
@@ -903,6 +931,89 @@ def ilu0_values(A, F, max_iter=0, tol=0.0, history=False, stream=None, f0_given=
                                         hist.ctypes.data if history else None, C.byref(info)))
     d = info.as_dict()
     return (F, d, hist[:d["sweeps"]].copy()) if history else (F, d)
+
+
+def _vec_f64(x, y):
+    if x.dtype != y.dtype or x.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("x and y must both be float32 or both float64 (got %s, %s)" % (x.dtype.name, y.dtype.name))
+    return 1 if x.dtype == np.dtype(np.float64) else 0
+
+
+def vec_dot(x, y, n=None, out=None, stream=None):
+    """sum_i x_i * y_i over the first n entries (default: all of x) of two float32 or two float64 DeviceArrays as a float64 in device
+    memory (bmsp_vec_dot): accumulated in double in the fixed tree include/bmsp.h writes out, so the result is a pure function of x, y and
+    n.  Asynchronous on `stream`.  Returns `out`, a float64 DeviceArray of one entry (made when None)."""
+    f64 = _vec_f64(x, y)
+    n = x.n if n is None else int(n)
+    if n > x.n or n > y.n:
+        raise ValueError("n = %d exceeds the arrays (%d, %d)" % (n, x.n, y.n))
+    if out is None:
+        out = DeviceArray(1, np.float64)
+    elif out.dtype != np.dtype(np.float64) or out.n < 1:
+        raise ValueError("out must hold one float64")
+    check(lib().bmsp_vec_dot(n, f64, x.ptr, y.ptr, out.ptr, stream))
+    return out
+
+
+def vec_axpby(a, x, b, y, n=None, stream=None):
+    """y = fl(fl(a * x) + fl(b * y)) over the first n entries (default: all of x), a and b rounded once to the vectors' type, every
+    operation rounded on its own; with b == 0 y is not read (bmsp_vec_axpby).  Asynchronous on `stream`.  Returns y."""
+    f64 = _vec_f64(x, y)
+    n = x.n if n is None else int(n)
+    if n > x.n or n > y.n:
+        raise ValueError("n = %d exceeds the arrays (%d, %d)" % (n, x.n, y.n))
+    check(lib().bmsp_vec_axpby(n, f64, float(a), x.ptr, float(b), y.ptr, stream))
+    return y
+
+
+def _precond(precond):
+    """None | "jacobi" | ("ilu", F) | ("ilu_sweeps", F, m) -> (Precond or None, the F to keep alive)"""
+    if precond is None or precond == "none":
+        return None, None
+    if precond == "jacobi":
+        return Precond(PC_JACOBI, None, 0), None
+    if isinstance(precond, Precond):
+        return precond, None
+    if isinstance(precond, (tuple, list)) and len(precond) == 2 and precond[0] == "ilu":
+        return Precond(PC_ILU_EXACT, precond[1].h, 0), precond[1]
+    if isinstance(precond, (tuple, list)) and len(precond) == 3 and precond[0] == "ilu_sweeps":
+        return Precond(PC_ILU_SWEEPS, precond[1].h, int(precond[2])), precond[1]
+    raise ValueError("precond must be None, 'jacobi', ('ilu', F) or ('ilu_sweeps', F, m) (got %r)" % (precond,))
+
+
+def krylov_solve(A, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+    """Solves op(A) * x = b on the device by preconditioned CG (method "cg", A symmetric positive definite) or BiCGStab ("bicgstab"), A
+    square, F32 or F64, in either tile layout (bmsp_krylov_solve).  precond: None, "jacobi", ("ilu", F) -- F from ilu0(), applied by two
+    spsv -- or ("ilu_sweeps", F, m) -- the same two solves by m spitsv sweeps each.  Stops when dot(r, r) <= tol^2 * dot(b, b), after
+    max_iter iterations (0: min(n, 2^20)) or on a breakdown; tol=KRYLOV_NO_CHECK runs exactly max_iter iterations asynchronously, nothing
+    read back (history must be False).  x: DeviceArray for the result (made when None; never b); x0_given: x holds the initial iterate
+    (default +0, x is not read).  The whole iteration is enqueued on `stream`; the scalars stay on the device.  Returns (x, info) or (x,
+    info, history): info = {"method", "iterations", "max_iterations", "status" (KRYLOV_MAXITER / _CONVERGED / _BREAKDOWN), "relres",
+    "bnorm", "products", "precond_applies", "workspace_bytes"}, history = the relative residual of every iteration (float64)."""
+    if method not in _METHODS:
+        raise ValueError("method must be 'cg' or 'bicgstab' (got %r)" % (method,))
+    pc, keep = _precond(precond)
+    i = A.info()
+    vt = np.dtype(OUT_DTYPE[i["dtype"]])
+    if b.dtype != vt or b.n < i["num_rows"]:
+        raise ValueError("b must hold %d entries of %s" % (i["num_rows"], vt.name))
+    if x is None:
+        if x0_given:
+            raise ValueError("x0_given needs x")
+        x = DeviceArray(i["num_rows"], vt)
+    elif x.dtype != vt or x.n < i["num_rows"]:
+        raise ValueError("x must hold %d entries of %s" % (i["num_rows"], vt.name))
+    info = KrylovInfo()
+    hist = None
+    if history:
+        cap = int(max_iter) if max_iter else min(i["num_rows"], 1 << 20)
+        hist = np.zeros(max(cap, 1), np.float64)
+    check(lib().bmsp_krylov_solve(A.h, _op(op), _METHODS[method], C.byref(pc) if pc is not None else None, b.ptr, x.ptr, int(max_iter),
+                                  float(tol), KRYLOV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info),
+                                  stream))
+    del keep
+    d = info.as_dict()
+    return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
 
 
 def _spsm_strides(k, ldb, ldx):

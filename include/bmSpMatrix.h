@@ -353,6 +353,31 @@ inline void bmSparse_ILU0_values(bmSpMatrix<ValueIn> &A, bmSpMatrix<ValueIn> &F,
     bmsp::check(bmsp_synchronize());
 }
 
+/* Krylov solvers (bmsp_krylov_solve): op(A) * x = b for a square float or double A in either tile layout by preconditioned CG
+ * (BMSP_KRYLOV_CG) or BiCGStab (BMSP_KRYLOV_BICGSTAB), the whole iteration enqueued on the device.  pc (may be null: none) names the
+ * preconditioner: BMSP_PC_JACOBI, or BMSP_PC_ILU_EXACT / BMSP_PC_ILU_SWEEPS with pc->F = F.handle() of a factor from bmSparse_ILU0.  Stops at
+ * dot(r, r) <= tol^2 * dot(b, b), after max_iter iterations (0: min(n, 2^20)) or on a breakdown (info->status); tol == BMSP_KRYLOV_NO_CHECK
+ * runs exactly max_iter iterations with nothing read back.  flags: BMSP_KRYLOV_X0_GIVEN = x holds the initial iterate (default +0).
+ * relres_history (host) and info may be null; synchronous like bmSparse_SpMV.  bmSparse_vec_dot is the solver's deterministic dot product
+ * of two device vectors (bmsp_vec_dot), returned to the host. */
+template <class ValueIn>
+inline void bmSparse_solve(bmSpMatrix<ValueIn> &A, int op, int method, const bmsp_precond *pc, const typename bmsp::vector_of<ValueIn>::type *b,
+                           typename bmsp::vector_of<ValueIn>::type *x, int64_t max_iter = 0, double tol = 1e-6, int flags = 0,
+                           double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
+{
+    bmsp::check(bmsp_krylov_solve(A.handle(), op, method, pc, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
+template <class R>
+inline double bmSparse_vec_dot(int64_t n, const R *x, const R *y)
+{
+    static_assert(sizeof(R) == 4 || sizeof(R) == 8, "float or double vectors");
+    bmsp::device_vector<double> out(1);
+    bmsp::check(bmsp_vec_dot(n, sizeof(R) == 8 ? 1 : 0, x, y, out.data(), nullptr));
+    bmsp::check(bmsp_synchronize());
+    return out.to_host()[0];
+}
+
 /* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are
  * device pointers to num_rows x k row-major arrays at leading dimensions ldb, ldx >= k (float, double for double); they may be the same
  * when ldb == ldx.  Column c of X holds the bits bmSparse_SpSV writes for column c of B, for one walk of the dependency chain instead of

@@ -596,6 +596,118 @@ int bmsp_matrix_ilu0(bmsp_matrix_t A, int64_t max_iter, double tol, int out_tran
 int bmsp_matrix_ilu0_values(bmsp_matrix_t A, bmsp_matrix_t F, int64_t max_iter, double tol, int flags, void *stream,
                             double *delta_history, bmsp_ilu0_info *info);
 
+/* Vector primitives of the Krylov solvers below, public because a caller's own iteration needs the same two: a deterministic dot product
+ * and a scaled sum.  Vectors are of the library's vector type R: float (vec_f64 == 0) or double (vec_f64 == 1); pointers need the
+ * alignment of an element and no more.  Both calls are asynchronous on `stream`; nothing in the reference is replaced.
+ *   bmsp_vec_dot: *d_result (a double in DEVICE memory) = sum_i x_i * y_i.  The result is a pure function of x, y and n: it does not
+ *       depend on the grid, on scheduling or on the stream, and there is no floating-point atomic.  The order, in full:
+ *         - accumulation in double for both vector types (the product of two floats is exact in double);
+ *         - the vector is cut into chunks of 1024 consecutive elements; chunk c starts at base = 1024 c;
+ *         - in a chunk, lane t of 256 starts with acc = +0 and for q = 0, 1, 2, 3 takes element i = base + 256 q + t: if i < n,
+ *           acc = fma((double)x_i, (double)y_i, acc);
+ *         - the 64 lanes of a wave (lanes 64 w .. 64 w + 63) are combined by the xor butterfly d = 32, 16, 8, 4, 2, 1 with
+ *           acc = acc + acc of lane (t xor d): addition commutes bit for bit, so every lane of the wave ends with the same value W[w];
+ *         - the chunk partial is P[c] = ((W[0] + W[1]) + W[2]) + W[3];
+ *         - the ceil(n / 1024) partials are combined by ONE workgroup the same way: lane t starts with acc = +0 and adds P[t], P[t + 256],
+ *           ... in ascending order with plain additions, then the same butterfly, then the same four-wave sum;
+ *         - n == 0 gives +0.
+ *       tests/krylov_ref.c restates this order in C.  Up to 384 chunks the second level is run by the workgroup that arrives last at an
+ *       integer ticket (its own partial goes out at agent scope and is drained, then the ticket; the last arriver reads every partial at
+ *       agent scope; it resets the ticket, so calls follow each other without a memset; nothing waits between workgroups: no flag, no
+ *       spin, no cooperative launch).  Beyond 384 chunks it is a launch of its own: the tickets are same-address atomics, about 11 ns each,
+ *       and cost more than a launch from about there (interpolated between measurements at 256 and 2048 chunks; DESIGN 4 "Krylov solvers").  BMSP_VEC_DOT_FINISH=ticket|launch (read per call, by
+ *       bmsp_krylov_solve too) forces one: the same bits, a measurement switch.  The partials and the ticket live in a scratch per device and stream that grows to
+ *       the largest n seen on that stream (growing it synchronises that stream) and is kept for the life of the process: calls on one
+ *       stream are ordered by it, calls on different streams share nothing, and the library serialises the enqueueing, so calls from
+ *       several threads are safe.
+ *   bmsp_vec_axpby: y_i = fl(fl(a * x_i) + fl(b * y_i)), the rule of the epilogues above: a and b are rounded once to R, each
+ *       operation is rounded on its own and never contracted; with b == 0 after that rounding y is not read (y_i = fl(a * x_i), a NaN in y
+ *       does not propagate).  x == y is legal.
+ *   Refused with BMSP_ERR_INVALID: n < 0; vec_f64 not 0 / 1; a null pointer while n > 0 (d_result always). */
+int bmsp_vec_dot(int64_t n, int vec_f64, const void *d_x, const void *d_y, double *d_result, void *stream);
+int bmsp_vec_axpby(int64_t n, int vec_f64, double a, const void *d_x, double b, void *d_y, void *stream);
+
+/* Krylov solvers on the device: op(A) x = b for a square A in EITHER tile layout by preconditioned conjugate gradients (A symmetric
+ * positive definite) or BiCGStab (van der Vorst's preconditioned form), with the whole iteration enqueued on `stream` -- products,
+ * preconditioner, dot products, vector updates and the scalars alpha, beta, omega, which never leave the device.  Nothing in the reference
+ * is replaced (it has no solver).
+ *   Operands: A is F32 or F64 (an F16 A is BMSP_ERR_UNSUPPORTED: the product's input vector would be fp16, and a Krylov basis in fp16 is
+ *       not this call); b and x are n vector elements of type R (float for F32, double for F64).  Every product is bmsp_spmv_op(A, op, 1, .,
+ *       0, .): no conversion, no second matrix.  A, b and the factor are not modified (their caches are built if missing).
+ *   Preconditioner z = M^-1 r (pc == NULL is BMSP_PC_NONE): BMSP_PC_JACOBI divides by the diagonal, one IEEE division per row, the diagonal
+ *       taken with bmsp_matrix_diagonal per call (a zero or unstored diagonal is not refused: IEEE gives Inf or NaN and the solve ends in
+ *       BMSP_KRYLOV_BREAKDOWN).  BMSP_PC_ILU_EXACT applies pc->F, a factor as bmsp_matrix_ilu0 makes it (L unit lower, U upper, either
+ *       layout), by two bmsp_spsv: (LOWER, UNIT) then (UPPER, NON_UNIT) under op N; under op T the transposed factors in the other order,
+ *       bmsp_spsv(F, T, UPPER, NON_UNIT) then (F, T, LOWER, UNIT).  BMSP_PC_ILU_SWEEPS: the same two solves by bmsp_spitsv with exactly
+ *       pc->sweeps sweeps each under BMSP_ITSV_NO_CHECK.  F is F64 for an F64 A and F32 or F16 for an F32 A (an F16 factor takes float
+ *       vectors in the solves).
+ *   Arithmetic, fixed operation by operation, so that x, iterations, status and the history are a pure function of the inputs wherever
+ *       the product is one (bmsp_spmv_op's view cases: op T, column-major A): dots are bmsp_vec_dot's; alpha, beta and omega are doubles
+ *       formed by one IEEE division each and rounded once to R (aR, bR, wR) before they touch a vector; every vector update is a separately
+ *       rounded multiply and a separately rounded add or subtract, never contracted.  bb = dot(b, b); thr = fl(fl(tol * tol) * bb) in double; a
+ *       residual with rr = dot(r, r) stops the iteration iff rr <= thr.  relres = sqrt(rr / bb) is formed on the host.  bb == 0: x = 0,
+ *       BMSP_KRYLOV_CONVERGED after 0 iterations.  x0 = +0 and d_x is not read, unless BMSP_KRYLOV_X0_GIVEN is set: then r = fl(b - op(A) x0),
+ *       one product more.  The initial residual is held to the same rule (rr0 = bb without x0): a start that already meets it returns
+ *       CONVERGED with 0 iterations.
+ *   CG: z = M^-1 r; p = z; rho = dot(r, z).  Iteration: q = op(A) p; alpha = rho / dot(p, q); x = fl(x + fl(aR * p)); r = fl(r - fl(aR * q));
+ *       rr = dot(r, r): record, stop?; z = M^-1 r; rho' = dot(r, z); beta = rho' / rho; rho = rho'; p = fl(z + fl(bR * p)).
+ *   BiCGStab: rh = r; rho' = dot(rh, r).  Iteration k: if k = 1 p = r, else beta = fl(fl(rho' / rho) * fl(alpha / omega)) and p = fl(r +
+ *       fl(bR * fl(p - fl(wR * v)))); rho = rho'; ph = M^-1 p; v = op(A) ph; alpha = rho / dot(rh, v); s = fl(r - fl(aR * v)); x = fl(x +
+ *       fl(aR * ph)); if dot(s, s) <= thr: record it, converged.  sh = M^-1 s; t = op(A) sh; omega = dot(t, s) / dot(t, t); x = fl(x + fl(wR *
+ *       sh)); r = fl(s - fl(wR * t)); rr = dot(r, r): record, stop?; rho' = dot(rh, r).
+ *       What the definitions allow is fused: the x and r updates with the partial sums of the dots that follow them, under Jacobi the
+ *       division too, and with BMSP_PC_NONE rho' IS rr (the same function of the same vector).  The bits are those of the unfused text.
+ *   Breakdown: a denominator (dot(p, q); dot(rh, v); dot(t, t); rho, checked when it is formed; omega, checked when it is formed) that is 0
+ *       or not finite, or a residual dot that is not finite -- or 0 where that is not convergence, under BMSP_KRYLOV_NO_CHECK -- ends the
+ *       solve with status BMSP_KRYLOV_BREAKDOWN.  It is a result, not an error: the call returns BMSP_OK.  x keeps the last iterate
+ *       WRITTEN, which is not always the last completed one: dot(p, q), dot(rh, v) and rho are checked before the update they would
+ *       scale, so x is then the iterate of the iteration before; BiCGStab's dot(t, t) and omega are checked after the half step x = fl(x +
+ *       fl(aR * ph)) has been applied, so x then holds that half step; a residual dot is checked after the update that produced it, so a
+ *       non-finite rr or dot(s, s) leaves the x it belongs to, which may itself hold non-finite values.  (Keeping the last completed
+ *       iterate instead would cost a second copy of x or one more launch per iteration; a caller who needs it keeps its own copy.)
+ *   Limits and modes: max_iter == 0 means min(n, 2^20).  tol == BMSP_KRYLOV_NO_CHECK, the inner-solver mode: exactly max_iter iterations
+ *       unless a breakdown stops them on the device; nothing is read back, relres_history must be NULL, info gets iterations = max_iter,
+ *       status = BMSP_KRYLOV_MAXITER, relres = bnorm = -1 and the products and applications of a full run.
+ *   Device-resident protocol, bmsp_spitsv's adapted: the scalars, the status and one record per iteration live in device memory; every
+ *       kernel of the solver begins by reading the status and returns without writing once the solve has stopped.  The host enqueues
+ *       BMSP_KRYLOV_CHECK=<iterations> iterations (read per call) between two read-backs of the records and decides by the same
+ *       predicate; without the variable the batches are 1, 2, 4, 8, then 16 iterations each.  The library calls in between (bmsp_spmv_op, bmsp_spsv, bmsp_spitsv) cannot return early: after a stop up to CHECK - 1
+ *       iterations of them run on unchanged vectors of the workspace and are wasted -- the trade the default is measured for: a solve
+ *       of one or two iterations with a costly preconditioner wants 1, a solve of hundreds 8 - 16, and the ramp serves both.  x,
+ *       iterations, status and the history never depend on BMSP_KRYLOV_CHECK or on the stream.
+ *   Results: x in d_x.  relres_history (host, may be NULL, max_iter entries or min(n, 2^20)): [k] = sqrt(rr_k / bb) of iteration k + 1, k <
+ *       iterations.  info (may be NULL): method by name ("cg" / "bicgstab" + "+none" / "+jacobi" / "+ilu" / "+ilu_sweeps"), the
+ *       iterations completed (each left a record), the cap that applied, the status, relres of the last record (of the initial
+ *       residual after 0 iterations), bnorm = sqrt(bb), the products and preconditioner applications whose results the solve consumed,
+ *       and the bytes of the workspace.
+ *   Workspace, kept on A's handle: 4 vectors for CG, 8 for BiCGStab, the diagonal, the dot partials, the scalars and the records,
+ *       sized for the largest need seen (growing it synchronises `stream`), freed with the handle and by bmsp_matrix_invalidate(A, 1).  One
+ *       stream per handle at a time, as for bmsp_spitsv (A's and F's).  Plans and views are built on first use by the calls that own them;
+ *       those builds synchronise.  After that a NO_CHECK call is fully asynchronous, and a checked call synchronises once for bb and
+ *       once per batch.
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing done on the device: op or method not
+ *   0 / 1; an unknown pc->kind; sweeps < 1 under BMSP_PC_ILU_SWEEPS; max_iter < 0 or > 2^20; tol NaN, or negative and not
+ *   BMSP_KRYLOV_NO_CHECK; flags with unknown bits; relres_history given under BMSP_KRYLOV_NO_CHECK; null A, d_b or d_x; d_x == d_b; a
+ *   non-square A; row-panel views; an ILU kind with a null F, with F's shape different from A's, or with an F dtype outside the rule
+ *   above.  A missing diagonal of F is refused by bmsp_spsv's own message.  BMSP_ERR_UNSUPPORTED: an F16 A. */
+#define BMSP_KRYLOV_CG 0
+#define BMSP_KRYLOV_BICGSTAB 1
+#define BMSP_PC_NONE 0
+#define BMSP_PC_JACOBI 1        /* z = r / diag(A), one IEEE division per row; the diagonal is taken with bmsp_matrix_diagonal per call */
+#define BMSP_PC_ILU_EXACT 2     /* z = U^-1 L^-1 r by two bmsp_spsv on F (F from bmsp_matrix_ilu0: L unit lower, U upper) */
+#define BMSP_PC_ILU_SWEEPS 3    /* the same two solves by bmsp_spitsv, exactly `sweeps` sweeps each, BMSP_ITSV_NO_CHECK */
+typedef struct { int kind; bmsp_matrix_t F; int64_t sweeps; } bmsp_precond;
+#define BMSP_KRYLOV_X0_GIVEN 1
+#define BMSP_KRYLOV_NO_CHECK (-1.0)
+#define BMSP_KRYLOV_MAXITER 0
+#define BMSP_KRYLOV_CONVERGED 1
+#define BMSP_KRYLOV_BREAKDOWN 2
+typedef struct { char method[32]; int64_t iterations, max_iterations; int status; double relres, bnorm;
+                 int64_t products, precond_applies, workspace_bytes; } bmsp_krylov_info;
+int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *pc /* NULL = none */, const void *d_b, void *d_x,
+                      int64_t max_iter, double tol, int flags, double *relres_history /* host, may be NULL */,
+                      bmsp_krylov_info *info /* may be NULL */, void *stream);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
