@@ -792,6 +792,37 @@ int bmsp_vec_axpby(int64_t n, int vec_f64, double a, const void *d_x, double b, 
     BMSP_API_END
 }
 
+int bmsp_matrix_color_blocks(bmsp_matrix_t A, uint64_t seed, uint32_t *d_colors, uint32_t *d_perm, void *stream, bmsp_color_info *info)
+{
+    BMSP_API_BEGIN
+    need(A, "matrix A"); need(d_colors, "d_colors");
+    color_check_matrix(A);
+    load_kernels();
+    color_blocks(A, seed, d_colors, d_perm, as_stream(stream), info);
+    BMSP_API_END
+}
+
+int bmsp_matrix_permute_blocks(bmsp_matrix_t A, const uint32_t *d_row_perm, const uint32_t *d_col_perm, int out_transposed, void *stream,
+                               bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    check_layout_flag(out_transposed, "out_transposed");
+    need(A, "matrix A"); need(out, "out");
+    permute_check_matrix(A);
+    load_kernels();
+    *out = permute_blocks(A, d_row_perm, d_col_perm, out_transposed, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int inverse, const void *d_x, void *d_y, void *stream)
+{
+    BMSP_API_BEGIN
+    vec_permute_check_args(n, vec_f64, d_perm, inverse, d_x, d_y);
+    load_kernels();
+    vec_permute_blocks(n, vec_f64, d_perm, inverse, d_x, d_y, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *pc, const void *d_b, void *d_x, int64_t max_iter, double tol,
                       int flags, double *relres_history, bmsp_krylov_info *info, void *stream)
 {

@@ -275,6 +275,18 @@ void sort_tiles_by_block_column(const bmsp_matrix_s *A, TileSort &ts, hipStream_
 // transpose.hip: out = A^T (swap) or A (!swap) with tiles in layout out_transposed; re-gather such an out's values from A
 bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st);
 void copy_values_from(bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
+// transpose.hip, for the makers that re-order whole tiles (reorder.hip): the value move through out's tile map and permutation flag, and
+// the tail of such a maker -- arrays, bitmaps and offsets in one scan, values, block-row pointer; synchronises `st`
+void move_values(const bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st);
+void finish_moved_tiles(bmsp_matrix_s *A, bmsp_matrix_s *m, hipStream_t st);
+// reorder.hip: the greedy colouring of the block-row graph by hashed priorities and the ordering by colour class; out = P * A * Q^T at
+// tile granularity (tiles in layout out_transposed; bmsp_matrix_copy_values replays it); the block permutation of a vector
+void color_check_matrix(const bmsp_matrix_s *A);
+void color_blocks(bmsp_matrix_s *A, uint64_t seed, uint32_t *d_colors, uint32_t *d_perm, hipStream_t st, bmsp_color_info *info);
+void permute_check_matrix(const bmsp_matrix_s *A);
+bmsp_matrix_s *permute_blocks(bmsp_matrix_s *A, const uint32_t *d_row_perm, const uint32_t *d_col_perm, int out_transposed, hipStream_t st);
+void vec_permute_check_args(int64_t n, int vec_f64, const void *d_perm, int inverse, const void *d_x, const void *d_y);
+void vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int inverse, const void *d_x, void *d_y, hipStream_t st);
 // add.hip: C = alpha*A + beta*B with tiles in layout out_transposed; re-compute such a C's values from the same two structures
 bmsp_matrix_s *add_matrices(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, int out_transposed, hipStream_t st);
 void add_values(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);

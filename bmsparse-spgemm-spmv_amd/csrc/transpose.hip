@@ -101,6 +101,8 @@ void launch_move(int g, const bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t 
     });
 }
 
+}  // namespace
+
 // moves the values of `out` from those of A through out's tile map (tp_map; null = same tile order) and permutation flag
 void move_values(const bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st)
 {
@@ -112,6 +114,8 @@ void move_values(const bmsp_matrix_s *A, bmsp_matrix_s *out, hipStream_t st)
         else launch_move<T, false>(g, A, out, st);
     });
 }
+
+namespace {
 
 void check_source(const bmsp_matrix_s *A, int out_transposed, const char *what)
 {
@@ -137,6 +141,23 @@ void sort_tiles_by_block_column(const bmsp_matrix_s *A, TileSort &ts, hipStream_
     ts.keys = kk.cur; ts.map = pp.cur;
 }
 
+// The tail that a transpose and a block permutation (reorder.hip) share.  m holds its dimensions, counts, dtype, layout and tp_*
+// fields and, when its tiles were re-ordered, its keys and tile map (m->keys null: A's tile order and keys).  Makes the other arrays,
+// writes bitmaps and offsets in one scan, moves the values and synchronises `st` (the sort temporaries go back to the pool).
+void finish_moved_tiles(bmsp_matrix_s *A, bmsp_matrix_s *m, hipStream_t st)
+{
+    const uint64_t nb = (uint64_t)A->block_num;
+    const bool keeps_keys = m->keys == nullptr;
+    alloc_tile_arrays(m, nb);  // (re-ordered tiles hold their keys already)
+    alloc_values(m, (uint64_t)m->nnz);
+    if (keeps_keys && nb) BMSP_HIP(hipMemcpyAsync(m->keys, A->keys, 8 * nb, hipMemcpyDeviceToDevice, st));
+    device_exclusive_scan<uint64_t>(OutCount{m->tp_map, A->bmps, nb}, OutTiles{m->tp_map, A->bmps, nb, m->tp_permute, m->bmps, m->offsets},
+                                    nb + 1, st);
+    move_values(A, m, st);
+    ensure_rowptr(m, st);
+    BMSP_HIP(hipStreamSynchronize(st));
+}
+
 // out = A^T (swap = true) or A (swap = false) with its tiles in layout out_transposed
 bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap, hipStream_t st)
 {
@@ -148,21 +169,13 @@ bmsp_matrix_s *transpose_matrix(bmsp_matrix_s *A, int out_transposed, bool swap,
     m->tp_src_uid = A->uid;
     // a transpose into the other layout, or a conversion into the same one, keeps every tile as it is
     m->tp_permute = (out_transposed != A->transposed) != swap ? 1 : 0;
-    const uint64_t nb = (uint64_t)A->block_num;
     TileSort ts;  // sort temporaries: go back to the pool after the synchronisation at the end
     if (swap) {
         sort_tiles_by_block_column(A, ts, st);
         m->keys = ts.take_keys();
         m->tp_map = ts.take_map();
     }
-    alloc_tile_arrays(m.get(), nb);  // (a transpose holds its keys already)
-    alloc_values(m.get(), m->nnz);
-    if (!swap && nb) BMSP_HIP(hipMemcpyAsync(m->keys, A->keys, 8 * nb, hipMemcpyDeviceToDevice, st));
-    device_exclusive_scan<uint64_t>(OutCount{m->tp_map, A->bmps, nb}, OutTiles{m->tp_map, A->bmps, nb, m->tp_permute, m->bmps, m->offsets},
-                                    nb + 1, st);
-    move_values(A, m.get(), st);
-    ensure_rowptr(m.get(), st);
-    BMSP_HIP(hipStreamSynchronize(st));
+    finish_moved_tiles(A, m.get(), st);
     return m.release();
 }
 

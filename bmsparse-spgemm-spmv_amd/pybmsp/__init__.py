@@ -51,7 +51,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -157,6 +157,15 @@ class Ilu0Info(C.Structure):
         return d
 
 
+class ColorInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("blocks", C.c_int64), ("colors", C.c_int64), ("rounds", C.c_int64), ("view_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
 class Precond(C.Structure):
     _fields_ = [("kind", C.c_int), ("F", C.c_void_p), ("sweeps", C.c_int64)]
 
@@ -254,7 +263,10 @@ def lib():
         L.bmsp_matrix_ilu0_values.argtypes = [vp, vp, i64, C.c_double, i, vp, vp, p(Ilu0Info)]
         L.bmsp_vec_dot.argtypes = [i64, i, vp, vp, vp, vp]
         L.bmsp_vec_axpby.argtypes = [i64, i, C.c_double, vp, C.c_double, vp, vp]
-        L.bmsp_krylov_solve.argtypes = [vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_matrix_color_blocks.argtypes = [vp, C.c_uint64, vp, vp, vp, p(ColorInfo)]
+        L.bmsp_matrix_permute_blocks.argtypes = [vp, vp, vp, i, vp, p(vp)]
+        L.bmsp_vec_permute_blocks.argtypes = [i64, i, vp, i, vp, vp, vp]
+        L.bmsp_krylov_solve.argtypes =[vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -582,6 +594,21 @@ class BmSpMatrix:
     def solve(self, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
         """(x, info[, history]) with op(this) * x = b by CG or BiCGStab on the device: pybmsp.krylov_solve"""
         return krylov_solve(self, b, method, precond, op, max_iter, tol, x, x0_given, history, stream)
+
+    def color_blocks(self, seed=0, stream=None):
+        """(colors, perm, info): the greedy block colouring by hashed priorities and its ordering: pybmsp.color_blocks"""
+        return color_blocks(self, seed, stream)
+
+    def permute_blocks(self, row_perm=None, col_perm=None, transposed=None, stream=None):
+        """P * this * Q^T at tile granularity as a new matrix: pybmsp.permute_blocks"""
+        return permute_blocks(self, row_perm, col_perm, transposed, stream)
+
+    def reorder_multicolor(self, seed=0, stream=None):
+        """(B, perm, info): this matrix under the symmetric block permutation by its multi-colour ordering, B = P * this * P^T, whose
+        triangular solves have info["colors"] levels (at most, with a trailing partial block-row); perm (new -> old) is what
+        vec_permute_blocks takes"""
+        _, perm, info = color_blocks(self, seed, stream)
+        return permute_blocks(self, perm, perm, None, stream), perm, info
 
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
@@ -963,6 +990,61 @@ def vec_axpby(a, x, b, y, n=None, stream=None):
     if n > x.n or n > y.n:
         raise ValueError("n = %d exceeds the arrays (%d, %d)" % (n, x.n, y.n))
     check(lib().bmsp_vec_axpby(n, f64, float(a), x.ptr, float(b), y.ptr, stream))
+    return y
+
+
+def color_blocks(A, seed=0, stream=None, want_perm=True):
+    """(colors, perm, info) of the greedy colouring of A's block-row graph by hashed priorities (bmsp_matrix_color_blocks): A square, any
+    dtype, either layout; block-rows I != J are neighbours iff a tile (I, J) or (J, I) is stored.  colors: uint32 DeviceArray of
+    ceil(n / 8) entries, a pure function of structure and seed; perm (new -> old; None with want_perm=False): the block-rows sorted by
+    (colour class, index), a trailing partial block-row kept last -- permute_blocks(A, perm, perm) has triangles of at most
+    info["colors"] levels.  info = {"kernel", "blocks", "colors", "rounds", "view_bytes"}.  Synchronises `stream`."""
+    nb = (A.info()["num_rows"] + 7) // 8
+    colors = DeviceArray(nb, np.uint32)
+    perm = DeviceArray(nb, np.uint32) if want_perm else None
+    info = ColorInfo()
+    check(lib().bmsp_matrix_color_blocks(A.h, int(seed) & 0xFFFFFFFFFFFFFFFF, colors.ptr, perm.ptr if want_perm else None, stream,
+                                         C.byref(info)))
+    return colors, perm, info.as_dict()
+
+
+def _block_perm(perm, blocks, name):
+    if perm is None:
+        return None
+    if perm.dtype != np.dtype(np.uint32) or perm.n < blocks:
+        raise ValueError("%s must hold %d entries of uint32" % (name, blocks))
+    return perm.ptr
+
+
+def permute_blocks(A, row_perm=None, col_perm=None, transposed=None, stream=None):
+    """P * A * Q^T at tile granularity as a new matrix with its tiles in layout `transposed` (None: A's): block (I', J') is block
+    (row_perm[I'], col_perm[J']) of A, the gather convention A[p][:, q] (bmsp_matrix_permute_blocks).  row_perm / col_perm: uint32
+    DeviceArrays of ceil(num_rows / 8) / ceil(num_cols / 8) entries, None = the identity; each is checked on the device to be a
+    permutation that keeps a trailing partial block in place.  Whole tiles move, values as raw bits; copy_values_from(A) replays a
+    value-only update of A.  Synchronises `stream`."""
+    i = A.info()
+    lay = i["transposed"] if transposed is None else int(transposed)
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_permute_blocks(A.h, _block_perm(row_perm, (i["num_rows"] + 7) // 8, "row_perm"),
+                                           _block_perm(col_perm, (i["num_cols"] + 7) // 8, "col_perm"), lay, stream, C.byref(h)))
+    return BmSpMatrix(h.value)
+
+
+def vec_permute_blocks(perm, x, inverse=False, y=None, n=None, stream=None):
+    """The block permutation of a float32 / float64 DeviceArray of n entries (default: all of x) by perm, a uint32 DeviceArray of
+    ceil(n / 8) entries (bmsp_vec_permute_blocks): y[8 i + r] = x[8 perm[i] + r] (b' = P b), or with inverse=True
+    y[8 perm[i] + r] = x[8 i + r] (x = P^T x').  y: made when None (zeroed), never x.  An entry of perm out of range is skipped.
+    Asynchronous on `stream`.  Returns y."""
+    n = x.n if n is None else int(n)
+    if y is None:
+        y = DeviceArray(n, x.dtype)
+        y.zero()
+    f64 = _vec_f64(x, y)
+    if n > x.n or n > y.n:
+        raise ValueError("n = %d exceeds the arrays (%d, %d)" % (n, x.n, y.n))
+    if perm.dtype != np.dtype(np.uint32) or perm.n < (n + 7) // 8:
+        raise ValueError("perm must hold %d entries of uint32" % ((n + 7) // 8))
+    check(lib().bmsp_vec_permute_blocks(n, f64, perm.ptr, int(inverse), x.ptr, y.ptr, stream))
     return y
 
 

@@ -212,6 +212,16 @@ public:
         out.reset(t);
         return out;
     }
+    /* P * A * Q^T at tile granularity (bmsp_matrix_permute_blocks): block (I', J') of the result is block (row_perm[I'], col_perm[J'])
+     * of this matrix; the permutations are device arrays of ceil(num_rows / 8) / ceil(num_cols / 8) entries, null = the identity */
+    bmSpMatrix<valueType> permute_blocks(const uint32_t *row_perm, const uint32_t *col_perm, bool transposed_layout) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_permute_blocks(h_, row_perm, col_perm, transposed_layout ? 1 : 0, nullptr, &t));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
 
     /* this matrix without the stored entries the rule drops (bmsp_matrix_prune): |v| <= tol under BMSP_PRUNE_ABS, |v| <= tol * rowmax
      * under BMSP_PRUNE_ROW_REL; tol = 0 drops the stored zeros a product or a sum leaves behind */
@@ -376,6 +386,38 @@ inline double bmSparse_vec_dot(int64_t n, const R *x, const R *y)
     bmsp::check(bmsp_vec_dot(n, sizeof(R) == 8 ? 1 : 0, x, y, out.data(), nullptr));
     bmsp::check(bmsp_synchronize());
     return out.to_host()[0];
+}
+
+/* Block multi-colour ordering and block permutation (bmsp_matrix_color_blocks / bmsp_matrix_permute_blocks / bmsp_vec_permute_blocks).
+ * bmSparse_color_blocks: the greedy colouring of the block-row graph of a square A by hashed priorities into colors and the ordering by
+ * colour class into perm (new -> old), both resized to ceil(num_rows / 8); the triangles of bmSparse_permute_blocks(A, perm, perm, B)
+ * have at most info->colors levels.  bmSparse_permute_blocks: B = P * A * Q^T at tile granularity, null = the identity.
+ * bmSparse_vec_permute_blocks: y[8 i + r] = x[8 perm[i] + r], or with inverse y[8 perm[i] + r] = x[8 i + r], on device vectors of n
+ * entries; y must not be x.  Synchronous like bmSparse_SpMV. */
+template <class ValueIn>
+inline void bmSparse_color_blocks(bmSpMatrix<ValueIn> &A, bmsp::device_vector<uint32_t> &colors, bmsp::device_vector<uint32_t> &perm,
+                                  uint64_t seed = 0, bmsp_color_info *info = nullptr)
+{
+    const size_t nb = ((size_t)A.num_rows + 7) / 8;
+    colors = bmsp::device_vector<uint32_t>(nb);
+    perm = bmsp::device_vector<uint32_t>(nb);
+    bmsp::check(bmsp_matrix_color_blocks(A.handle(), seed, colors.data(), perm.data(), nullptr, info));
+    bmsp::check(bmsp_synchronize());
+}
+template <class valueType>
+inline void bmSparse_permute_blocks(bmSpMatrix<valueType> &A, const uint32_t *row_perm, const uint32_t *col_perm, bmSpMatrix<valueType> &B,
+                                    bool transposed_layout = false)
+{
+    bmsp_matrix_t b = nullptr;
+    bmsp::check(bmsp_matrix_permute_blocks(A.handle(), row_perm, col_perm, transposed_layout ? 1 : 0, nullptr, &b));
+    B.reset(b);
+}
+template <class R>
+inline void bmSparse_vec_permute_blocks(int64_t n, const uint32_t *perm, const R *x, R *y, bool inverse = false)
+{
+    static_assert(sizeof(R) == 4 || sizeof(R) == 8, "float or double vectors");
+    bmsp::check(bmsp_vec_permute_blocks(n, sizeof(R) == 8 ? 1 : 0, perm, inverse ? 1 : 0, x, y, nullptr));
+    bmsp::check(bmsp_synchronize());
 }
 
 /* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are

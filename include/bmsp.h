@@ -38,7 +38,8 @@ typedef enum {
     BMSP_ERR_HIP = -3,       /* a HIP runtime call failed */
     BMSP_ERR_NOMEM = -4,
     BMSP_ERR_UNSUPPORTED = -5,
-    BMSP_ERR_LIMIT = -6      /* a 32-bit internal limit would overflow */
+    BMSP_ERR_LIMIT = -6,     /* a 32-bit internal limit would overflow */
+    BMSP_ERR_INTERNAL = -7   /* a bound the library proves for itself did not hold (bmsp_matrix_color_blocks: more rounds than blocks) */
 } bmsp_status;
 
 typedef enum { BMSP_F32 = 0, BMSP_F16 = 1, BMSP_F64 = 2 } bmsp_dtype;
@@ -626,6 +627,67 @@ int bmsp_matrix_ilu0_values(bmsp_matrix_t A, bmsp_matrix_t F, int64_t max_iter, 
  *   Refused with BMSP_ERR_INVALID: n < 0; vec_f64 not 0 / 1; a null pointer while n > 0 (d_result always). */
 int bmsp_vec_dot(int64_t n, int vec_f64, const void *d_x, const void *d_y, double *d_result, void *stream);
 int bmsp_vec_axpby(int64_t n, int vec_f64, double a, const void *d_x, double b, void *d_y, void *stream);
+
+/* Block multi-colour ordering and block permutation on the device: what a solver that reorders needs, without the round trip through
+ * bmsp_matrix_to_coo_device and a builder.  The level rule of bmsp_spsv counts tiles and ignores bitmaps, so a proper colouring of the
+ * block-row graph with every colour class made contiguous gives a matrix whose triangular solves have as many levels as there are
+ * colours; bmsp_spsv, bmsp_spsm, bmsp_spitsv, bmsp_matrix_ilu0 and the preconditioners of bmsp_krylov_solve work on it unchanged.  Nothing
+ * in the reference is replaced.
+ *
+ *   bmsp_matrix_color_blocks: the greedy colouring of the block-row graph of a square A (any dtype, either layout; structure only) by
+ *       hashed priorities, and the ordering by colour class.  d_colors and d_perm hold nb = ceil(n / 8) entries of DEVICE memory.
+ *       Graph: block-rows I != J are neighbours iff a tile (I, J) or a tile (J, I) is stored, whatever its bitmap -- the dependency rule
+ *           of bmsp_spsv, symmetrised (a lower-triangular A colours like A + A^T).  The neighbours come from A's own keys and block-row
+ *           pointer and from the cached op-T view of bmsp_spmv_op (built if missing, which synchronises `stream`); A + A^T is not formed.
+ *       Colours, a pure function of structure and seed: key(I) = (splitmix64(seed ^ I), I) compared lexicographically as unsigned
+ *           (splitmix64: z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *           z ^ z >> 31).  color(I) is the smallest c >= 0 that no neighbour with a greater key holds (the sequential greedy colouring in
+ *           descending key order); round(I) is 1 without a greater-key neighbour, else 1 + the largest round among them.  A block-row
+ *           without tiles or neighbours gets colour 0.  Nothing depends on scheduling, lane counts or the stream.
+ *       info (may be NULL): kernel = "color_round_kernel<8 lanes>" ("none (empty matrix)" for n = 0); blocks = nb; colors = 1 + the
+ *           largest colour (0 for n = 0); rounds = the largest round; view_bytes = the op-T view's size.
+ *       d_perm (may be NULL), new -> old: the block-rows sorted by (class, index), classes in ascending colour order.  When n % 8 != 0
+ *           the class of the trailing partial block-row goes last (that block-row is then last within it), which keeps the permuted matrix
+ *           n x n.  The triangles of bmsp_matrix_permute_blocks(A, d_perm, d_perm) then have at most `colors` levels, exactly `colors`
+ *           when n % 8 == 0 and A's block pattern is symmetric (a tile (J, I) for every tile (I, J): a block-row of colour c has a
+ *           neighbour of every smaller colour in front of it, which is a dependency only where the tile lies in that triangle).
+ *       Kernel (Jones-Plassmann; vector ALU): one launch per round, eight lanes per block-row.  A block-row is coloured in round k iff
+ *           every greater-key neighbour carries the stamp of a round before k; a colour written in the current launch reads as
+ *           "uncoloured".  No waiting between workgroups: no flag, no spin, no cooperative launch.  The smallest free colour is found in
+ *           windows of 64 colours (a 64-bit mask ORed over the neighbours; first zero bit; a full mask moves the window).  The block-rows
+ *           left uncoloured are counted per round by integer atomics (one per workgroup); a launch that finds the count of the round before
+ *           at 0 returns at once.  The host enqueues BMSP_COLOR_CHECK rounds (default 16, read per call), reads the counts back and stops
+ *           at the first 0: the switch decides how much is enqueued ahead, never the result.  At most nb rounds are run, since every
+ *           round colours the greatest remaining key; passing that bound returns BMSP_ERR_INTERNAL.  Synchronises `stream`.
+ *       Refused with BMSP_ERR_INVALID, the message naming the argument: null A or d_colors; a non-square A; a row-panel view.
+ *       BMSP_ERR_LIMIT: as for bmsp_spsv.
+ *
+ *   bmsp_matrix_permute_blocks: out = P * A * Q^T at tile granularity, a fresh pool-owned handle with its tiles in layout out_transposed:
+ *       block (I', J') of out is block (d_row_perm[I'], d_col_perm[J']) of A -- the gather convention A[p][:, q], the one d_perm above
+ *       follows; NULL = the identity.  Any dtype, rectangular A, either input and either output layout; dimensions, nnz and the tile
+ *       count are A's; the four arrays equal, bit for bit, what the builders make from the permuted COO.  Values move as raw bits; A and
+ *       its caches are untouched.  Passes: the inverses of the permutations; the new key per tile; a stable radix sort over the new
+ *       key's bits with the source tile as payload (new rows alone: the row bits only -- the input is in (row, column) order; new
+ *       columns need both halves; neither: no sort); one scan that writes bitmaps and offsets; the value move of bmsp_matrix_transpose
+ *       (bitmaps transposed and values permuted inside tiles exactly when out_transposed differs from A's layout).  No COO round
+ *       trip, no atomics outside the check.  bmsp_matrix_copy_values(A, out) replays a value-only update of A.
+ *       Checked on the device before anything is built (scatter marks and a count, one 8-byte read-back; no index is used unchecked):
+ *       each given array is a permutation of [0, block count), and when the dimension is not a multiple of 8 the last block maps to
+ *       itself; otherwise BMSP_ERR_INVALID naming the argument, and *out is left untouched.  Also refused: null A or out;
+ *       out_transposed not 0 / 1; row-panel views.  BMSP_ERR_LIMIT: as for bmsp_matrix_transpose.  Runs on `stream` and synchronises
+ *       it: at the read-back of the check and before it returns (the sort temporaries go back to the pool).
+ *
+ *   bmsp_vec_permute_blocks: the vectors that go with it, float (vec_f64 == 0) or double (1), d_perm of ceil(n / 8) entries.
+ *       inverse == 0: y[8 i + r] = x[8 perm[i] + r] (b' = P b); inverse == 1: y[8 perm[i] + r] = x[8 i + r] (x = P^T x'); both for
+ *       8 i + r < n and 8 perm[i] + r < n, other entries of y are not written.  Asynchronous on `stream`, nothing is read back.  The
+ *       permutation is not validated: an entry perm[i] >= ceil(n / 8) is skipped, and no access outside [0, n) of x or y is ever made.
+ *       Refused with BMSP_ERR_INVALID: n < 0; vec_f64 or inverse not 0 / 1; while n > 0, a null pointer or d_x == d_y. */
+typedef struct { char kernel[64]; int64_t blocks, colors, rounds, view_bytes; } bmsp_color_info;
+int bmsp_matrix_color_blocks(bmsp_matrix_t A, uint64_t seed, uint32_t *d_colors, uint32_t *d_perm /* may be NULL */,
+                             void *stream, bmsp_color_info *info /* may be NULL */);
+int bmsp_matrix_permute_blocks(bmsp_matrix_t A, const uint32_t *d_row_perm /* NULL = identity */,
+                               const uint32_t *d_col_perm /* NULL = identity */, int out_transposed, void *stream, bmsp_matrix_t *out);
+int bmsp_vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int inverse, const void *d_x, void *d_y, void *stream);
 
 /* Krylov solvers on the device: op(A) x = b for a square A in EITHER tile layout by preconditioned conjugate gradients (A symmetric
  * positive definite) or BiCGStab (van der Vorst's preconditioned form), with the whole iteration enqueued on `stream` -- products,
