@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void rs_fill_kernel(const uint64_t *__res
     if (br >= block_rows) return;
     const int lane = lane_id();
     const uint32_t t0 = block_rowptr[br], t1 = block_rowptr[br + 1];
-    // rows 0-3 in `lo`, rows 4-7 in `hi`: four 16-bit fields each (a block-row of 2^13 tiles of 8 values per row stays below 2^16)
+    // rows 0-3 in `lo`, rows 4-7 in `hi`: four 16-bit fields each (a block-row of fewer than kRsRowBlocksEnd = 2^13 tiles of 8 values per row stays below 2^16)
     uint64_t carry_lo = 0, carry_hi = 0;
     for (uint32_t base = t0; base < t1; base += 64) {
         const uint32_t t = base + (uint32_t)lane;
@@ -307,7 +307,7 @@ void ensure_csr32(bmsp_matrix_s *m, hipStream_t st)
     const uint32_t rows = (uint32_t)m->num_rows;
     ensure_rowptr(m, st);
     ensure_row_stats(m, st);
-    if (m->max_row_blocks >= (1 << 13)) fail(BMSP_ERR_LIMIT, "row-sparse block-MAC: a block-row of 8192 or more tiles");
+    if (m->max_row_blocks >= kRsRowBlocksEnd) fail(BMSP_ERR_LIMIT, "row-sparse block-MAC: a block-row of 8192 or more tiles");  // (internal guard: the callers ask first)
     m->csr_rowptr = (uint32_t *)pool_alloc(4 * ((size_t)rows + 1));
     m->csr_ent = (uint32_t *)pool_alloc(8 * (size_t)(n ? n : 1));
     const uint32_t nbr_c = (uint32_t)m->num_block_rows();
@@ -335,8 +335,10 @@ void ensure_csr32(bmsp_matrix_s *m, hipStream_t st)
 // Operands of nearly empty tiles (at most 16 stored values per tile on average on both sides) whose product takes V15's numerics -- fp32
 // operands under any tc_version, fp16 operands under tc_version 5: the scalar products that exist are a few per cent of what a
 // tile-by-tile kernel multiplies.  Needs finite values and, for fp32, every product of stored values a normal number (biased exponents
-// summing to >= 128); the caller bounds the block-rows of C by mac_strip_row_cap() tiles.  BMSP_MAC_ROWSPARSE=0/1: never / whatever
-// the fill.
+// summing to >= 128) and every block-row of both operands below kRsRowBlocksEnd tiles (the CSR copy's 16-bit row counters: an operand
+// with a longer block-row takes the kernels that read tiles -- lane tiles and the strip kernel, the fp32 MFMA task-list kernel, the
+// vector-ALU kernel); the caller bounds the block-rows of C by mac_strip_row_cap() tiles.  BMSP_MAC_ROWSPARSE=0/1: never / whatever
+// the fill (the fill rule only: every other condition holds under 1 as well).
 bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st)
 {
     const char *e = getenv("BMSP_MAC_ROWSPARSE");
@@ -344,6 +346,9 @@ bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, h
     if (A->dtype != B->dtype || (A->dtype != BMSP_F32 && !(A->dtype == BMSP_F16 && tc_version == 5))) return false;
     if ((uint64_t)A->nnz >= (1ull << 29) || (uint64_t)B->nnz >= (1ull << 29)) return false;  // (8-byte entries behind 32-bit byte offsets)
     if (A->view_values_end || B->view_values_end || A->ownership == 2 || B->ownership == 2) return false;  // (row-panel views: no copy of their own)
+    ensure_row_stats(A, st);
+    ensure_row_stats(B, st);
+    if (A->max_row_blocks >= kRsRowBlocksEnd || B->max_row_blocks >= kRsRowBlocksEnd) return false;  // (no CSR copy of such a block-row: ensure_csr32)
     if (!(e && e[0] == '1') && !(A->nnz <= 16 * A->block_num && B->nnz <= 16 * B->block_num)) return false;
     ensure_finite_flag(A, st);
     ensure_finite_flag(B, st);

@@ -228,6 +228,9 @@ bool mac_strip_fits_c(bmsp_matrix_s *C, hipStream_t st);
 uint32_t mac_strip_row_cap();
 int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st);  // returns the BMSP_MAC_* variant that ran (strip, or row-sparse for V15 numerics on nearly empty tiles)
 bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);  // a numeric stage that works from C's structure alone exists for these operands
+// the row-sparse kernel's CSR copy counts a block-row's values per matrix row in 16-bit fields (8 values per tile and row): a block-row of
+// this many tiles or more has no such copy -- mac_rowsparse_applies and prepare_spgemm_operand ask first, ensure_csr32 refuses
+constexpr int64_t kRsRowBlocksEnd = 1 << 13;
 void ensure_csr32(bmsp_matrix_s *m, hipStream_t st);
 bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);
 void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);

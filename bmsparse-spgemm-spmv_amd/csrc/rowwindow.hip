@@ -229,6 +229,8 @@ struct WinArgs {
 #define BMSP_WIN_WAVES 8
 #endif
 constexpr int kWinWaves = BMSP_WIN_WAVES;       // waves per workgroup
+static_assert(kHashCap + 64u * kWinWaves < (uint32_t)kHashSlots,
+              "slot_insert / slot_find end only while a hashed window's table keeps an empty slot: kHashCap tiles and one step of every wave");
 constexpr int kWinThreads = 64 * kWinWaves;
 constexpr int kWinBatch = 4;                    // steps whose records a wave requests together, fill pass (8-byte half records)
 constexpr int kWinBatchCount = 4;               // ... count pass (16-byte records)
