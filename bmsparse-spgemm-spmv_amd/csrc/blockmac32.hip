@@ -507,33 +507,12 @@ void ensure_dense_tiles(bmsp_matrix_s *m, hipStream_t st)
         device_for_each(ExpandDense<float>{m->bmps, m->offsets, (const float *)m->values, (float *)m->dense_tiles}, (uint64_t)m->block_num * 64, st);
 }
 
-// true when the kernel can run this product (32-bit byte offsets into the dense copies and the records)
-bool mac_mfma32_supported(const bmsp_matrix_s *A, const bmsp_matrix_s *B)
-{
-    return A->dtype == BMSP_F16 && A->block_num < (1ll << 25) && B->block_num < (1ll << 25) && (uint64_t)B->values_extent() * 2 + 16 < (1ull << 32);
-}
-
-// which operand form B takes.  Measured (block-MAC log): the dense copy wins on every generator case -- the kernel is bound
-// by instruction issue and LDS traffic, not by bytes, and the dense line needs no block record and no nibble decode (cage-like
-// 421 vs 468 us, R-MAT 2^16 2.58 vs 2.91 ms, full tiles 72 vs 84 us) -- at 128 B per block of extra memory and ~2x the L2 miss
-// traffic.  So: dense unless the copy would be large (> 4 GiB) and the tiles are sparse, or BMSP_MAC_B_DENSE says otherwise;
-// always dense when the value array is borrowed without the read slack the 12-byte nibble loads need.
-bool mac_mfma32_b_dense(const bmsp_matrix_s *B)
-{
-    const char *force = getenv("BMSP_MAC_B_DENSE");  // experiment / test switch (read per call)
-    if (force) return force[0] == '1';
-    if (!pool_owns(B->values)) return true;
-    const bool full_tiles = B->block_num && (double)B->nnz / (double)B->block_num >= 32.0;
-    return full_tiles || (uint64_t)B->block_num * 128ull <= (4ull << 30);
-}
-
-int launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
-                      bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st)
+// b_dense: B from its dense copy (else from the records); direct: operand lines straight into the MFMA lanes, no LDS (mac_choice.h decides both)
+void launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
+                       bmsp_matrix_s *B, bmsp_matrix_s *C, bool b_dense, bool direct, hipStream_t st)
 {
     const uint32_t cs = (uint32_t)C->block_num;
-    if (!cs) return BMSP_MAC_STAGED;
     ensure_dense_tiles(A, st);
-    const bool b_dense = mac_mfma32_b_dense(B);
     if (b_dense) ensure_dense_tiles(B, st);
     else ensure_block_meta(B, st);
     Mac32Args g{};
@@ -545,9 +524,6 @@ int launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *t
     g.c_bmps = C->bmps; g.c_offs = C->offsets; g.c_vals = (float *)C->values; g.c_size = cs;
     // equal task quotas per wave, a multiple of 64 (c_of_wave is indexed per 64 tasks); ~8 quotas per resident wave slot so
     // that hub tiles and uneven tiles-per-task do not leave a tail
-    // >= 4.6 tasks per C tile: the direct kernel (no LDS); sparser task lists keep the staged one (BMSP_MAC_DIRECT = 0 / 1 forces)
-    const char *de = getenv("BMSP_MAC_DIRECT");
-    const bool direct = b_dense && (de ? de[0] == '1' : 10 * n_tasks >= 46 * (uint64_t)cs);
     const char *qenv = getenv("BMSP_MAC_QUOTA");
     // (measured, T_7 in us at 256 / 512 / 1024 / 2048 / 4096 tasks per wave: R-MAT 2^16 x 8 2586 / 2496 / 2511 / 2548 / 2699, cage-like 427 (128) /
     // 421 (512) / 454 (2048): short quotas keep an XCD's resident waves on few block-rows of B at a time -- capped at 512 while that leaves
@@ -582,7 +558,6 @@ int launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *t
     else if (v == 28) hipLaunchKernelGGL((block_mac_mfma32_kernel<kW, false, 28>), dim3(grid), dim3(kThreads), 0, st, g);
     else hipLaunchKernelGGL((block_mac_mfma32_kernel<kW, false, 0>), dim3(grid), dim3(kThreads), 0, st, g);
     BMSP_CHECK_LAUNCH();
-    return direct ? BMSP_MAC_DIRECT : BMSP_MAC_STAGED;
 }
 
 // runs the lane-layout self test; returns the number of mismatching elements of the 16x16 result

@@ -275,23 +275,11 @@ bool mac_f32_mfma_usable(hipStream_t st)
     return g_f32_chain_ok == 1;
 }
 
-// fp32 operands through the MFMA kernel; false = not taken (the caller launches the vector-ALU kernel)
-bool launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
+// fp32 operands through the MFMA kernel (opt-in, and only while every product is a normal number: mac_choice.h)
+void launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
                          bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st)
 {
-    // Opt-in (BMSP_MAC_F32MFMA=1).  Measured on MI355X the kernel is bound by the 256 bytes it reads per operand tile and beats neither
-    // vector-ALU kernel: FEM-like product (3.7 values per tile) T_7 1.71 ms vs 1.62 ms for the element-gather kernel, full-tile banded
-    // 127 us vs 96 us for the dense-staged one (block-MAC log round 3).  Kept, with its parity tests, as the measured answer to
-    // "does the fp32 MFMA help V15".
-    const char *force = getenv("BMSP_MAC_F32MFMA");
-    if (!force || force[0] != '1') return false;
-    if (A->dtype != BMSP_F32 || n_tasks >= (1ull << 29) || A->block_num >= (1ll << 24) || B->block_num >= (1ll << 24)) return false;
     const uint32_t cs = (uint32_t)C->block_num;
-    if (!mac_f32_mfma_usable(st)) return false;
-    // (the instruction is the fmaf chain only while every product is a normal number: see mac_strip_operands_ok)
-    ensure_finite_flag(A, st);
-    ensure_finite_flag(B, st);
-    if (A->values_finite != 1 || B->values_finite != 1 || A->f32_exp_min + B->f32_exp_min < mac_f32_exp_floor(st) || A->f32_exp_max + B->f32_exp_max > 354) return false;
     ensure_lane_tiles(A, st);
     ensure_lane_tiles(B, st);
     MacF32Args g{};
@@ -312,7 +300,6 @@ bool launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t
     else if (du == 8) hipLaunchKernelGGL(block_mac_f32_mfma_kernel<8>, grid, dim3(kThreads), 0, st, g);
     else hipLaunchKernelGGL(block_mac_f32_mfma_kernel<2>, grid, dim3(kThreads), 0, st, g);
     BMSP_CHECK_LAUNCH();
-    return true;
 }
 
 }  // namespace bmsp

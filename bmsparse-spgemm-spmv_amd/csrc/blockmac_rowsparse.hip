@@ -9,7 +9,7 @@
 //   for every stored A(i, k), k ascending:   for every stored B(k, j):   C(i, j) = fmaf(A(i, k), B(k, j), C(i, j))
 // with the reference's zero terms left out.  A zero term changes a sum only when the sum is -0 (fmaf(0, b, -0) = +0), and a sum is -0
 // only after a product has underflowed: the launcher takes this kernel only for operands whose exponent ranges keep every product of
-// stored values a normal number (the precondition of the fp32 matrix-core kernel, mac_strip_operands_ok), and for finite values (0 x inf).
+// stored values a normal number (kRsExpSumMin, mac_choice.h), and for finite values (0 x inf).
 //
 // One workgroup (L / 8 waves) per block-row of C; C's structure is given (T_3 ... T_9 have fixed it).  Accumulators: one float per stored
 // value of the block-row, in LDS (a window of C tiles of at most kRsAcc values at a time; a block-row that holds more is walked once per
@@ -28,10 +28,9 @@
 namespace bmsp {
 namespace {
 
-// the table of a block-row's C columns: 2^HB slots.  HB = 9 for at most 256 tiles (strip mode's bound; 17.1 KB of LDS: nine workgroups per
-// CU -- a 385-entry offset array made it eight, FEM-like T_7 285 -> 324 us) or 10 for at most 768 (products that come with a task list,
+// the table of a block-row's C columns: 2^HB slots, rs_row_cap(HB) tiles (mac_choice.h).  HB = 9 (strip mode's bound; 17.1 KB of LDS: nine
+// workgroups per CU -- a 385-entry offset array made it eight, FEM-like T_7 285 -> 324 us) or 10 (products that come with a task list,
 // cage-like block-rows of 400 - 600 tiles; 27 KB, five workgroups per CU)
-constexpr uint32_t rs_row_cap(int hb) { return hb == 9 ? 256u : 768u; }
 constexpr uint32_t kRsAcc = 2048;     // accumulators per window
 constexpr uint32_t kRsEmpty = 0xffffffffu;
 
@@ -332,38 +331,7 @@ void ensure_csr32(bmsp_matrix_s *m, hipStream_t st)
     }
 }
 
-// Operands of nearly empty tiles (at most 16 stored values per tile on average on both sides) whose product takes V15's numerics -- fp32
-// operands under any tc_version, fp16 operands under tc_version 5: the scalar products that exist are a few per cent of what a
-// tile-by-tile kernel multiplies.  Needs finite values and, for fp32, every product of stored values a normal number (biased exponents
-// summing to >= 128) and every block-row of both operands below kRsRowBlocksEnd tiles (the CSR copy's 16-bit row counters: an operand
-// with a longer block-row takes the kernels that read tiles -- lane tiles and the strip kernel, the fp32 MFMA task-list kernel, the
-// vector-ALU kernel); the caller bounds the block-rows of C by mac_strip_row_cap() tiles.  BMSP_MAC_ROWSPARSE=0/1: never / whatever
-// the fill (the fill rule only: every other condition holds under 1 as well).
-bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st)
-{
-    const char *e = getenv("BMSP_MAC_ROWSPARSE");
-    if (e && e[0] == '0') return false;
-    if (A->dtype != B->dtype || (A->dtype != BMSP_F32 && !(A->dtype == BMSP_F16 && tc_version == 5))) return false;
-    if ((uint64_t)A->nnz >= (1ull << 29) || (uint64_t)B->nnz >= (1ull << 29)) return false;  // (8-byte entries behind 32-bit byte offsets)
-    if (A->view_values_end || B->view_values_end || A->ownership == 2 || B->ownership == 2) return false;  // (row-panel views: no copy of their own)
-    ensure_row_stats(A, st);
-    ensure_row_stats(B, st);
-    if (A->max_row_blocks >= kRsRowBlocksEnd || B->max_row_blocks >= kRsRowBlocksEnd) return false;  // (no CSR copy of such a block-row: ensure_csr32)
-    if (!(e && e[0] == '1') && !(A->nnz <= 16 * A->block_num && B->nnz <= 16 * B->block_num)) return false;
-    ensure_finite_flag(A, st);
-    ensure_finite_flag(B, st);
-    if (A->values_finite != 1 || B->values_finite != 1) return false;
-    return A->dtype != BMSP_F32 || A->f32_exp_min + B->f32_exp_min >= 128;
-}
-
-// every block-row of C within the larger table's capacity
-bool mac_rowsparse_fits_c(bmsp_matrix_s *C, hipStream_t st)
-{
-    if (C->block_num >= (1ll << 31) || C->block_num == 0) return false;
-    ensure_row_stats(C, st);
-    return (uint64_t)C->max_row_blocks <= rs_row_cap(10);
-}
-
+// (when the kernel applies: mac_choice.h -- it has bounded every block-row of C by rs_row_cap(10) tiles)
 void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st)
 {
     ensure_csr32(A, st);
@@ -383,7 +351,7 @@ void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, 
     const dim3 grid(g.block_rows), block(8u * (unsigned)lanes);
     const bool half = A->dtype == BMSP_F16;
     ensure_row_stats(C, st);
-    const bool big = (uint64_t)C->max_row_blocks > rs_row_cap(9);  // (mac_rowsparse_fits_c has bounded it by rs_row_cap(10))
+    const bool big = (uint64_t)C->max_row_blocks > rs_row_cap(9);
 #define BMSP_RS_LAUNCH(L_, H_, B_) hipLaunchKernelGGL((block_mac_rowsparse_kernel<L_, H_, B_>), grid, block, 0, st, g)
 #define BMSP_RS_PICK(L_) \
     do { \

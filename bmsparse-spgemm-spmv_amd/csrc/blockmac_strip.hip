@@ -26,7 +26,7 @@
 // k-group ahead), binary-search the window's columns in LDS and scatter the tile index into the schedule; the MFMA lanes then fetch
 // their B line (one 16-byte line per lane) for up to four active column pairs at a time and issue the MFMAs.
 //
-// Limits (the launcher checks them and keeps the task-list kernels of blockmac32.hip otherwise): <= kKCap merged A tiles and <= kJCap
+// Limits (the rule of mac_choice.h checks them and keeps the task-list kernels of blockmac32.hip otherwise): <= kKCap merged A tiles and <= kJCap
 // merged C tiles per strip, finite operand values (a skipped pair's product must be an exact zero), 32-bit byte offsets.
 #include "mac_common.hip.h"
 
@@ -37,8 +37,7 @@ typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x2k_t __attribute__((ext_vector_type(2)));
 typedef float f32x2k_t __attribute__((ext_vector_type(2)));
 
-constexpr int kKCap = 192;  // merged A tiles of a strip (two block-rows)
-constexpr int kJCap = 512;  // merged C tiles of a strip
+// (kKCap merged A tiles and kJCap merged C tiles of a strip: mac_choice.h, beside the rule that checks them)
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr int kStageTile = 72;             // floats per staged C tile: 64 + 8, so the four tiles of a pair start in different LDS banks
 constexpr uint32_t kNoTile = 0xffffff00u;  // schedule word of an absent tile: a byte offset no line offset brings back into a buffer
@@ -587,71 +586,10 @@ void ensure_finite_flag(bmsp_matrix_s *m, hipStream_t st)
     m->values_finite = h[0] == 255ull ? 0 : 1;
 }
 
-// what the strip kernel needs of the operands alone: fp16 tiles the K = 32 MFMA path addresses, a strip's merged A tiles within the k
-// list, finite values (cached per-matrix figures; the read-backs behind them happen once per matrix)
-bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st)
-{
-    if (A->dtype == BMSP_F16) {
-        if (!mac_mfma32_supported(A, B)) return false;
-    } else if (A->dtype == BMSP_F32) {
-        // 256-byte tiles behind 32-bit byte offsets; the instruction's summation order is checked on the device once per process
-        if (B->dtype != BMSP_F32 || A->block_num >= (1ll << 24) || B->block_num >= (1ll << 24) || !mac_f32_mfma_usable(st)) return false;
-        // every product a normal number (|a| |b| >= 2^(ea + eb - 254) >= 2^-126) and every sum far from overflow: outside that range the
-        // matrix pipe's rounding is not the fmaf chain's, and V15's vector-ALU kernel (task-list mode or the pipeline) takes the product
-        ensure_finite_flag(A, st);
-        ensure_finite_flag(B, st);
-        if (A->f32_exp_min + B->f32_exp_min < mac_f32_exp_floor(st) || A->f32_exp_max + B->f32_exp_max > 254 + 100) return false;
-    } else {
-        return false;
-    }
-    if ((uint64_t)A->num_block_rows() >= (1ull << 31)) return false;
-    ensure_row_stats(A, st);
-    if (2 * A->max_row_blocks > kKCap) return false;
-    ensure_finite_flag(A, st);
-    ensure_finite_flag(B, st);
-    return A->values_finite == 1 && B->values_finite == 1;
-}
-
-// ... and of C: a strip's merged C tiles within the column list (two block-rows of at most mac_strip_row_cap() tiles always fit)
-uint32_t mac_strip_row_cap() { return (uint32_t)kJCap / 2u; }
-bool mac_strip_fits_c(bmsp_matrix_s *C, hipStream_t st)
-{
-    if (C->block_num >= (1ll << 31) || C->block_num == 0) return false;
-    ensure_row_stats(C, st);
-    return 2 * C->max_row_blocks <= kJCap;
-}
-
-// whether the strip kernel takes a product whose task list exists (the task-list kernels are the alternative)
-bool mac_strip_eligible(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, uint64_t candidates, uint64_t n_tasks, hipStream_t st)
-{
-    const char *force = getenv("BMSP_MAC_STRIP");  // 0 / 1: experiment and test switch (the capacity limits still hold)
-    if (force && force[0] == '0') return false;
-    if (!force) {
-        // The walk visits every candidate pair and pays a fixed price per (window, k-group) item: it wins where items are fat -- C tiles
-        // that collect many tasks from candidate pairs that nearly all survive (dense-tile ceiling: 32.8 tasks per C tile, 840 us against
-        // 1430 us for the direct kernel).  On the FEM-like product (14 tasks per C tile, 61 % of the pairs survive, 3 MFMAs per item) the
-        // direct kernel stays ahead (530 vs 640 us), so the bar sits between the two.
-        if (n_tasks < 20 * (uint64_t)C->block_num || 10 * n_tasks < 9 * candidates) return false;
-    }
-    return mac_strip_fits_c(C, st) && mac_strip_operands_ok(A, B, st);
-}
-
-// the numeric stages that need no task list: the row-sparse kernel (V15 numerics on nearly empty tiles) or the strip kernels
-bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st)
-{
-    if (mac_rowsparse_applies(A, B, tc_version, st)) return true;
-    if (A->dtype == BMSP_F16 && tc_version != 4) return false;  // the fp16 strip kernel has the matrix cores' numerics
-    return mac_strip_operands_ok(A, B, st);
-}
-
-int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st)
+// launches the strip kernel of the operands' value type (whether it applies: mac_choice.h)
+void launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, bool prof, hipStream_t st)
 {
     const bool f32 = A->dtype == BMSP_F32;
-    // V15 numerics on nearly empty tiles: only the scalar products that exist (blockmac_rowsparse.hip)
-    if (!getenv("BMSP_STRIP_PROF") && mac_rowsparse_applies(A, B, tc_version, st)) {
-        launch_mac_rowsparse(A, B, C, st);
-        return BMSP_MAC_ROWSPARSE;
-    }
     if (f32) { ensure_lane_tiles(A, st); ensure_lane_tiles(B, st); }
     else { ensure_dense_tiles(A, st); ensure_dense_tiles(B, st); }
     ensure_rowptr(A, st);
@@ -673,7 +611,7 @@ int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int t
     // of the 803 us kernel on the ceiling case: the next item's scan run twice +208 us, the B lines requested out of range -99 us; C tiles
     // leaving as 256-byte runs through LDS instead of per-value stores: 803 -> 776 us.
     const dim3 grid((strips + 3) / 4);
-    if (getenv("BMSP_STRIP_PROF")) {  // timing build: per-phase timer ticks, printed per launch
+    if (prof) {  // timing build: per-phase timer ticks, printed per launch
         DevBuf<unsigned long long> prof(8);
         BMSP_HIP(hipMemsetAsync(prof.p, 0, 64, st));
         g.prof = prof.p;
@@ -686,13 +624,12 @@ int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int t
         const double w = (double)(h[5] ? h[5] : 1);
         fprintf(stderr, "strip prof (ticks per wave, %llu waves): set-up %.0f  scans %.0f  requests+lines+mfma %.0f (of which waiting for lines, fp32 build: %.0f)  stores %.0f  whole %.0f\n", h[5], h[0] / w,
                 h[1] / w, h[2] / w, h[6] / w, h[3] / w, h[4] / w);
-        return BMSP_MAC_STRIP;
+        return;
     }
     if (f32) hipLaunchKernelGGL((block_mac_strip_kernel<16, 8, 3, true>), grid, dim3(kThreads), 0, st, g);
     else if (getenv("BMSP_STRIP_WIDE")) hipLaunchKernelGGL((block_mac_strip_kernel<16, 16, 2>), grid, dim3(kThreads), 0, st, g);  // experiment switch
     else hipLaunchKernelGGL((block_mac_strip_kernel<16, 8, 3>), grid, dim3(kThreads), 0, st, g);
     BMSP_CHECK_LAUNCH();
-    return BMSP_MAC_STRIP;
 }
 
 }  // namespace bmsp

@@ -725,22 +725,21 @@ int tile_product_selftest(hipStream_t st)
 
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st)
 {
-    if ((uint64_t)m->values_extent() >= (1ull << 32) || m->block_num >= (1ll << 28)) return;  // pointer-based block-MAC: no records
-    ensure_block_meta(m, st);
-    // K = 32 MFMA block-MAC: A (normal layout) is always read from its dense copy, B from the dense copy or from the records
-    if (m->dtype == BMSP_F16 && m->block_num < (1ll << 25) && (!m->transposed || mac_mfma32_b_dense(m))) ensure_dense_tiles(m, st);
-    // V15 block-MAC (tc_version 5): fp32 operands with tiles at least a quarter full are staged from a dense copy too (256 B per block)
-    if (m->dtype == BMSP_F32 && m->nnz >= 16 * m->block_num && (uint64_t)m->block_num * 256 <= (4ull << 30)) ensure_dense_tiles(m, st);
-    // fp32 operands of nearly empty tiles: the row-sparse block-MAC's CSR copy (8 B per value) -- what such a matrix is multiplied from;
-    // otherwise the fp32 strip block-MAC's (and the opt-in fp32 MFMA task-list kernel's) tiles in MFMA lane order (256 B per block).
-    // (fp16 operands take the row-sparse kernel only under tc_version 5: their copy is made by the first such product; a matrix with a
-    // block-row of kRsRowBlocksEnd tiles or more has no CSR copy and is multiplied from its tiles: mac_rowsparse_applies)
-    const char *rse = getenv("BMSP_MAC_ROWSPARSE");
-    ensure_row_stats(m, st);
-    const bool sparse_tiles = m->nnz <= 16 * m->block_num && (uint64_t)m->nnz < (1ull << 29) && !m->view_values_end && m->ownership != 2 && !(rse && rse[0] == '0') &&
-                              m->max_row_blocks < kRsRowBlocksEnd;
-    if (m->dtype == BMSP_F32 && sparse_tiles) ensure_csr32(m, st);
-    else if (m->dtype == BMSP_F32 && m->block_num < (1ll << 24) && mac_f32_mfma_usable(st)) ensure_lane_tiles(m, st);
+    // the operand forms the block-MAC kernels would read of this matrix: the per-operand halves of the rule (mac_choice.h).  The forms
+    // it has settled on before it names a fact it needs are built first (each ensure_* returns at once the second time)
+    const MacSwitches sw = mac_read_switches();
+    int f32_chain_ok = -1;
+    for (;;) {
+        const MacPrepare p = mac_prepare_forms(mac_operand_facts(m), m->transposed != 0, f32_chain_ok, sw);
+        if (!p.forms) return;
+        if (p.forms & kMacFormBlockMeta) ensure_block_meta(m, st);
+        if (p.forms & kMacFormDenseTiles) ensure_dense_tiles(m, st);
+        if (p.forms & kMacFormCsr) ensure_csr32(m, st);
+        if (p.forms & kMacFormLaneTiles) ensure_lane_tiles(m, st);
+        if (p.need == MacNeed::None) break;
+        if (p.need == MacNeed::RowStatsA) ensure_row_stats(m, st);
+        else f32_chain_ok = mac_f32_mfma_usable(st) ? 1 : 0;
+    }
     // what decides whether a product takes the row-merge path: block-row pointer and maxima, "every stored value is finite"
     ensure_row_stats(m, st);
     if (m->ownership != 2 || !m->view_block_begin) ensure_struct_hash(m, st);

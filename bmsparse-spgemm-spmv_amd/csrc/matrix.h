@@ -3,6 +3,7 @@
 #ifndef BMSP_MATRIX_H_
 #define BMSP_MATRIX_H_
 
+#include "mac_choice.h"
 #include "runtime.h"
 #include <memory>
 #include <vector>
@@ -167,7 +168,7 @@ inline void rm_hint_key(bmsp_matrix_s *m, uint64_t partner)
 // a strip pass that overflowed on a panel overflows on every matrix that holds the panel's block-rows (2 stays), a panel that fitted
 // says so until another panel or the parent's own pass says otherwise, and of the list paths the one that corrects itself wins (a pair
 // sent to the column windows that does not need them ends in the pipeline and remembers that; the reverse never happens).  A view that
-// ran no strip pass -- the predicates refuse views where they accept the parent (mac_rowsparse_applies) -- has written nothing about
+// ran no strip pass -- the rule refuses views where it accepts the parent (mac_rowsparse_operand) -- has written nothing about
 // strip mode, so nothing of the kind reaches the parent.
 inline void rm_hint_inherit(bmsp_matrix_s *view, const bmsp_matrix_s *parent)
 {
@@ -213,28 +214,27 @@ void ensure_dense_tiles(bmsp_matrix_s *m, hipStream_t st);
 void ensure_lane_tiles(bmsp_matrix_s *m, hipStream_t st);
 void ensure_finite_flag(bmsp_matrix_s *m, hipStream_t st);
 bool mac_f32_mfma_usable(hipStream_t st);
-bool mac_mfma32_supported(const bmsp_matrix_s *A, const bmsp_matrix_s *B);
-bool mac_mfma32_b_dense(const bmsp_matrix_s *B);
-int launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
-                      bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);  // returns the variant it launched (BMSP_MAC_*)
 int mfma32_selftest(hipStream_t st);
 int mfma_f32_selftest(hipStream_t st, bool cancel = false);
 int mac_f32_exp_floor(hipStream_t st);
-bool launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
-                         bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
-bool mac_strip_eligible(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, uint64_t candidates, uint64_t n_tasks, hipStream_t st);
-bool mac_strip_operands_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, hipStream_t st);
-bool mac_strip_fits_c(bmsp_matrix_s *C, hipStream_t st);
-uint32_t mac_strip_row_cap();
-int launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc_version, hipStream_t st);  // returns the BMSP_MAC_* variant that ran (strip, or row-sparse for V15 numerics on nearly empty tiles)
-bool mac_structure_numeric_ok(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);  // a numeric stage that works from C's structure alone exists for these operands
-// the row-sparse kernel's CSR copy counts a block-row's values per matrix row in 16-bit fields (8 values per tile and row): a block-row of
-// this many tiles or more has no such copy -- mac_rowsparse_applies and prepare_spgemm_operand ask first, ensure_csr32 refuses
-constexpr int64_t kRsRowBlocksEnd = 1 << 13;
 void ensure_csr32(bmsp_matrix_s *m, hipStream_t st);
-bool mac_rowsparse_applies(bmsp_matrix_s *A, bmsp_matrix_s *B, int tc_version, hipStream_t st);
+// Which block-MAC kernel a product takes is decided in ONE place: the pure rule of mac_choice.h, asked through mac_decide (mac_choice.hip),
+// which copies the facts out of the handles and fetches the costly ones only when the rule names them.  bmsp_spgemm, bmsp_spgemm_numeric
+// and bmsp_matrix_prepare(SPGEMM) ask it and nothing else; the launchers below launch what they are told and keep only their tuning.
+struct MacTasks {  // a product's sorted task list
+    const uint64_t *sorted;
+    uint64_t n, candidates;
+    const uint32_t *begin, *c_of_wave;
+};
+MacSwitches mac_read_switches();
+MacOperand mac_operand_facts(const bmsp_matrix_s *m);
+MacChoice mac_decide(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const MacTasks *tasks, int tc_version, const MacSwitches &sw, hipStream_t st);
+void launch_mac_mfma32(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
+                       bmsp_matrix_s *B, bmsp_matrix_s *C, bool b_dense, bool direct, hipStream_t st);
+void launch_mac_f32_mfma(const uint64_t *tasks, uint64_t n_tasks, const uint32_t *task_begin, const uint32_t *c_of_wave, bmsp_matrix_s *A,
+                         bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
+void launch_mac_strip(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, bool prof, hipStream_t st);  // prof: the timing build (BMSP_STRIP_PROF)
 void launch_mac_rowsparse(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);
-bool mac_rowsparse_fits_c(bmsp_matrix_s *C, hipStream_t st);  // every block-row of C within the row-sparse kernel's table (768 tiles)
 bool rowmerge_symbolic(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const uint64_t *first_pos, uint64_t total, uint32_t row_cap,
                        uint64_t *surviving, uint64_t *candidates, hipStream_t st);
 bool rowmerge_tasklist(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const uint64_t *first_pos, uint64_t total, DevBuf<uint64_t> &tasks,

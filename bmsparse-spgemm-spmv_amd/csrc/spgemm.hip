@@ -861,48 +861,40 @@ __global__ __launch_bounds__(kThreads) void block_mac_valu_group_kernel(const ui
     }
 }
 
+// the vector-ALU forms (V15 numerics from a task list): staged from dense copies, element gathers, or -- value arrays beyond the 4 GiB a
+// buffer descriptor addresses -- the pointer-based kernel (which of them: mac_choice.h)
 template <typename T>
-void launch_mac_valu(const uint64_t *tasks, const uint32_t *task_begin, bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C,
-                     hipStream_t st)
+void launch_mac_valu(MacPath path, const uint64_t *tasks, const uint32_t *task_begin, bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st)
 {
-    uint32_t cs = (uint32_t)C->block_num;
-    if (!cs) return;
+    const uint32_t cs = (uint32_t)C->block_num;
     const uint64_t a_bytes = (uint64_t)A->values_extent() * sizeof(T), b_bytes = (uint64_t)B->values_extent() * sizeof(T);
-    if (a_bytes < (1ull << 32) && b_bytes < (1ull << 32) && A->block_num < (1ll << 28) && B->block_num < (1ll << 28)) {
-        ensure_block_meta(A, st);
-        ensure_block_meta(B, st);
-        const uint32_t groups = (cs + kValuGroupC - 1) / kValuGroupC;
-        uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
-        if constexpr (sizeof(T) == 2 || sizeof(T) == 4) {
-            // fp16 / fp32: stage the tiles from their dense copies (64 elements per block: 128 / 256 B; BMSP_MAC_VALU_DENSE=0 keeps the element
-            // gathers, and so does a copy above 4 GiB)
-            const char *de = getenv("BMSP_MAC_VALU_DENSE");
-            const uint64_t per_block = 64 * sizeof(T);
-            // fp16 copies exist anyway (the MFMA kernels' operands).  An fp32 copy is 256 B per block: taken when the tiles are at least a
-            // quarter full (the copy is then <= 4x the values; FEM-like 3.7 values per tile: 17x the memory for -10 % of T_7, not taken)
-            const bool worth = sizeof(T) == 2 || (A->nnz >= 16 * A->block_num && B->nnz >= 16 * B->block_num);
-            const bool dense = de ? de[0] == '1'
-                                  : (worth && (uint64_t)A->block_num * per_block <= (4ull << 30) && (uint64_t)B->block_num * per_block <= (4ull << 30));
-            if (dense) {
-                ensure_dense_tiles(A, st);
-                ensure_dense_tiles(B, st);
-                hipLaunchKernelGGL((block_mac_valu_group_kernel<T, kValuGroupC, kValuBatch, true>), dim3(grid), dim3(kThreads), 0, st, tasks, task_begin,
-                                   A->block_meta, (uint32_t)(A->block_num * 16), (const T *)A->values, B->block_meta, (uint32_t)(B->block_num * 16),
-                                   (const T *)B->values, C->bmps, C->offsets, (typename MacOps<T>::Out *)C->values, cs, (uint32_t)a_bytes,
-                                   (uint32_t)b_bytes, (const u32x4_t *)A->dense_tiles, (const u32x4_t *)B->dense_tiles);
-                BMSP_CHECK_LAUNCH();
-                return;
-            }
-        }
-        hipLaunchKernelGGL((block_mac_valu_group_kernel<T, kValuGroupC, kValuBatch>), dim3(grid), dim3(kThreads), 0, st, tasks, task_begin, A->block_meta,
-                           (uint32_t)(A->block_num * 16), (const T *)A->values, B->block_meta, (uint32_t)(B->block_num * 16), (const T *)B->values,
-                           C->bmps, C->offsets, (typename MacOps<T>::Out *)C->values, cs, (uint32_t)a_bytes, (uint32_t)b_bytes);
-    } else {  // value arrays beyond the 4 GiB a buffer descriptor addresses: pointer-based kernel
+    if (path == MacPath::ValuPointer) {
         uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)cs + 3) / 4, 256ull * 64);
         hipLaunchKernelGGL((block_mac_valu_kernel<T>), dim3(grid), dim3(kThreads), 0, st, tasks, task_begin, A->bmps, A->offsets,
                            (const T *)A->values, B->bmps, B->offsets, (const T *)B->values, C->bmps, C->offsets,
                            (typename MacOps<T>::Out *)C->values, cs);
+        BMSP_CHECK_LAUNCH();
+        return;
     }
+    ensure_block_meta(A, st);
+    ensure_block_meta(B, st);
+    const uint32_t groups = (cs + kValuGroupC - 1) / kValuGroupC;
+    uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
+    if constexpr (sizeof(T) == 2 || sizeof(T) == 4) {
+        if (path == MacPath::ValuDense) {  // the tiles staged from their dense copies (64 elements per block: 128 / 256 B)
+            ensure_dense_tiles(A, st);
+            ensure_dense_tiles(B, st);
+            hipLaunchKernelGGL((block_mac_valu_group_kernel<T, kValuGroupC, kValuBatch, true>), dim3(grid), dim3(kThreads), 0, st, tasks, task_begin,
+                               A->block_meta, (uint32_t)(A->block_num * 16), (const T *)A->values, B->block_meta, (uint32_t)(B->block_num * 16),
+                               (const T *)B->values, C->bmps, C->offsets, (typename MacOps<T>::Out *)C->values, cs, (uint32_t)a_bytes,
+                               (uint32_t)b_bytes, (const u32x4_t *)A->dense_tiles, (const u32x4_t *)B->dense_tiles);
+            BMSP_CHECK_LAUNCH();
+            return;
+        }
+    }
+    hipLaunchKernelGGL((block_mac_valu_group_kernel<T, kValuGroupC, kValuBatch>), dim3(grid), dim3(kThreads), 0, st, tasks, task_begin, A->block_meta,
+                       (uint32_t)(A->block_num * 16), (const T *)A->values, B->block_meta, (uint32_t)(B->block_num * 16), (const T *)B->values,
+                       C->bmps, C->offsets, (typename MacOps<T>::Out *)C->values, cs, (uint32_t)a_bytes, (uint32_t)b_bytes);
     BMSP_CHECK_LAUNCH();
 }
 
@@ -914,56 +906,74 @@ void print_stage(bool verbose, const char *name, double us)
 
 }  // namespace
 
-// T_7 from a sorted task list: the block multiply-accumulate kernel of the tc_version and value type (shared by the whole product and by
-// bmsp_spgemm_numeric on a C that kept its list)
-static void launch_block_mac(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const uint64_t *tasks_sorted, uint64_t n_tasks, const uint32_t *task_begin,
-                             const uint32_t *c_of_wave, uint64_t total, int tc_version, bool mfma, bmsp_spgemm_stats *S, hipStream_t st)
+// the switches of the symbolic paths.  BMSP_SPGEMM_ROWMERGE=0 switches the row-merge paths off, =1 takes them under an explicit sort mode
+// too, =2 skips strip mode; BMSP_SPGEMM_ROWWINDOW=0: never the column-window passes (rowwindow.hip), =1: always, whatever the operands
+// look like (tests)
+struct PathSwitches {
+    bool rm_force, rm_off, rm_no_strip, win_off, win_force;
+    bool strip_mode_off() const { return rm_off || rm_no_strip || win_force; }
+};
+static PathSwitches read_path_switches()
+{
+    const char *rme = getenv("BMSP_SPGEMM_ROWMERGE"), *we = getenv("BMSP_SPGEMM_ROWWINDOW");
+    return {rme && rme[0] != '0', rme && rme[0] == '0', rme && rme[0] == '2', we && we[0] == '0', we && we[0] == '1'};
+}
+
+// T_7: launches the kernel mac_decide chose (shared by the whole product and by bmsp_spgemm_numeric) and reports it
+static void launch_block_mac(const MacChoice &ch, bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const MacTasks *tasks, const MacSwitches &sw,
+                             bmsp_spgemm_stats *S, hipStream_t st)
 {
     const uint32_t c_size = (uint32_t)C->block_num;
-    if (mfma) {
-        if ((uint64_t)A->values_extent() * 2 + 16 >= (1ull << 32) || (uint64_t)B->values_extent() * 2 + 16 >= (1ull << 32))
-            fail(BMSP_ERR_LIMIT, "MFMA block-MAC addresses operand values through 4 GiB buffer descriptors; use tc_version 5");
-        // the group kernel's 12-byte value loads may run past the last stored value: arrays from this library's
-        // allocator carry that slack (runtime.h), borrowed arrays (bmsp_matrix_from_arrays, ownership 2) may not
-        const uint32_t a_bytes = (uint32_t)(A->values_extent() * 2), b_bytes = (uint32_t)(B->values_extent() * 2);
-        const bool old_mac = getenv("BMSP_MAC_OLD") != nullptr;  // experiment switch: the r1 16x16x16 group kernel
-        if (tc_version == 4 && !old_mac && mac_mfma32_supported(A, B)) {
-            // many tasks per C tile and most candidate pairs alive: the strip kernel (operand reuse; reads A, B, C, not the task list)
-            if (mac_strip_eligible(A, B, C, total, n_tasks, st)) {
-                S->mac_variant = launch_mac_strip(A, B, C, tc_version, st);
-            } else {
-                S->mac_variant = launch_mac_mfma32(tasks_sorted, n_tasks, task_begin, c_of_wave, A, B, C, st);
-            }
-        } else if (tc_version == 4 && pool_owns(A->values) && pool_owns(B->values) && A->block_num < (1ll << 28) && B->block_num < (1ll << 28)) {
-            ensure_block_meta(A, st);
-            ensure_block_meta(B, st);
-            uint32_t groups = (c_size + kGroupC - 1) / kGroupC;
-            uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
-            hipLaunchKernelGGL(block_mac_mfma_f16_group_kernel, dim3(grid), dim3(kThreads), 0, st, tasks_sorted, task_begin, A->block_meta,
-                               (uint32_t)(A->block_num * 16), (const _Float16 *)A->values, B->block_meta, (uint32_t)(B->block_num * 16),
-                               (const _Float16 *)B->values, C->bmps, C->offsets, (float *)C->values, c_size, a_bytes + 16u, b_bytes + 16u);
-        } else {
-            uint32_t groups = ((c_size + 1) / 2 + kPairsPerWave - 1) / kPairsPerWave;
-            uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
-            hipLaunchKernelGGL(block_mac_mfma_f16_kernel, dim3(grid), dim3(kThreads), 0, st, tasks_sorted, task_begin, A->bmps, A->offsets,
-                               (const _Float16 *)A->values, B->bmps, B->offsets, (const _Float16 *)B->values, C->bmps, C->offsets,
-                               (float *)C->values, c_size, a_bytes, b_bytes);
-        }
+    const uint32_t a_bytes = (uint32_t)(A->values_extent() * 2), b_bytes = (uint32_t)(B->values_extent() * 2);  // (the fp16 kernels')
+    S->mac_kernel = ch.mac_kernel;
+    S->mac_variant = ch.mac_variant;
+    switch (ch.path) {
+    case MacPath::None: fail(BMSP_ERR_INTERNAL, "no block-MAC kernel chosen");
+    case MacPath::RowSparse: launch_mac_rowsparse(A, B, C, st); return;
+    case MacPath::StripF16:
+    case MacPath::StripF32: launch_mac_strip(A, B, C, sw.strip_prof >= 0, st); return;
+    case MacPath::Mfma32Staged:
+    case MacPath::Mfma32Direct:
+        launch_mac_mfma32(tasks->sorted, tasks->n, tasks->begin, tasks->c_of_wave, A, B, C, (ch.b_forms & kMacFormDenseTiles) != 0, ch.path == MacPath::Mfma32Direct, st);
+        return;
+    case MacPath::Mfma16Group: {
+        ensure_block_meta(A, st);
+        ensure_block_meta(B, st);
+        uint32_t groups = (c_size + kGroupC - 1) / kGroupC;
+        uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
+        hipLaunchKernelGGL(block_mac_mfma_f16_group_kernel, dim3(grid), dim3(kThreads), 0, st, tasks->sorted, tasks->begin, A->block_meta,
+                           (uint32_t)(A->block_num * 16), (const _Float16 *)A->values, B->block_meta, (uint32_t)(B->block_num * 16),
+                           (const _Float16 *)B->values, C->bmps, C->offsets, (float *)C->values, c_size, a_bytes + 16u, b_bytes + 16u);
         BMSP_CHECK_LAUNCH();
-        S->mac_kernel = tc_version;
-    } else if (A->dtype != BMSP_F64 && !getenv("BMSP_MAC_VALU_DENSE") && !getenv("BMSP_MAC_F32MFMA") && mac_rowsparse_applies(A, B, tc_version, st) &&
-               mac_rowsparse_fits_c(C, st)) {
-        // V15 numerics on operands of nearly empty tiles: the products of stored values only (blockmac_rowsparse.hip); the task list is not read
-        launch_mac_rowsparse(A, B, C, st);
-        S->mac_variant = BMSP_MAC_ROWSPARSE;
-        S->mac_kernel = 5;
-    } else {
-        if (A->dtype == BMSP_F32 && launch_mac_f32_mfma(tasks_sorted, n_tasks, task_begin, c_of_wave, A, B, C, st)) S->mac_variant = BMSP_MAC_F32MFMA;
-        else if (A->dtype == BMSP_F32) launch_mac_valu<float>(tasks_sorted, task_begin, A, B, C, st);
-        else if (A->dtype == BMSP_F16) launch_mac_valu<_Float16>(tasks_sorted, task_begin, A, B, C, st);
-        else launch_mac_valu<double>(tasks_sorted, task_begin, A, B, C, st);
-        S->mac_kernel = 5;
+        return;
     }
+    case MacPath::Mfma16: {
+        uint32_t groups = ((c_size + 1) / 2 + kPairsPerWave - 1) / kPairsPerWave;
+        uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)groups + 3) / 4, 256ull * 64);
+        hipLaunchKernelGGL(block_mac_mfma_f16_kernel, dim3(grid), dim3(kThreads), 0, st, tasks->sorted, tasks->begin, A->bmps, A->offsets,
+                           (const _Float16 *)A->values, B->bmps, B->offsets, (const _Float16 *)B->values, C->bmps, C->offsets,
+                           (float *)C->values, c_size, a_bytes, b_bytes);
+        BMSP_CHECK_LAUNCH();
+        return;
+    }
+    case MacPath::F32Mfma: launch_mac_f32_mfma(tasks->sorted, tasks->n, tasks->begin, tasks->c_of_wave, A, B, C, st); return;
+    case MacPath::ValuDense:
+    case MacPath::ValuGather:
+    case MacPath::ValuPointer:
+        if (A->dtype == BMSP_F32) launch_mac_valu<float>(ch.path, tasks->sorted, tasks->begin, A, B, C, st);
+        else if (A->dtype == BMSP_F16) launch_mac_valu<_Float16>(ch.path, tasks->sorted, tasks->begin, A, B, C, st);
+        else launch_mac_valu<double>(ch.path, tasks->sorted, tasks->begin, A, B, C, st);
+        return;
+    }
+}
+
+// T_7 from a sorted task list: the kernel of the tc_version and value type
+static void block_mac_from_tasks(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, const MacTasks &tasks, int tc_version, const MacSwitches &sw,
+                                 bmsp_spgemm_stats *S, hipStream_t st)
+{
+    if (A->dtype == BMSP_F16 && tc_version != 5 && ((uint64_t)A->values_extent() * 2 + 16 >= (1ull << 32) || (uint64_t)B->values_extent() * 2 + 16 >= (1ull << 32)))
+        fail(BMSP_ERR_LIMIT, "MFMA block-MAC addresses operand values through 4 GiB buffer descriptors; use tc_version 5");
+    launch_block_mac(mac_decide(A, B, C, &tasks, tc_version, sw, st), A, B, C, &tasks, sw, S, st);
 }
 
 void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, int tc_version, int verbose, hipStream_t st,
@@ -976,7 +986,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
     if (A->dtype != B->dtype) fail(BMSP_ERR_INVALID, "A and B must have the same value type");
     if (mode < 0 || mode > 2) fail(BMSP_ERR_INVALID, "sort mode must be 0, 1 or 2");
     if (tc_version < 1 || tc_version > 5) fail(BMSP_ERR_INVALID, "tc_version must be 1..5");
-    const bool mfma = tc_version != 5 && A->dtype == BMSP_F16;
+    const MacSwitches sw = mac_read_switches();
 
     bmsp_spgemm_stats local{};
     bmsp_spgemm_stats *S = stats ? stats : &local;
@@ -1064,17 +1074,14 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
     };
 
     // Row-merge paths (rowmerge.hip): C's structure formed block-row by block-row in LDS instead of expand - sort - compress.  Taken when
-    // the sort mode is left to the library.  (1) Strip mode -- one pass, no task list, numeric stage by the strip kernel -- when the
-    // operands fit that kernel and every block-row of C holds at most mac_strip_row_cap() tiles; (2) task-list mode -- a count pass and a
-    // fill pass that also writes the sorted task list, numeric stage by the task-list kernels of the tc_version -- for block-rows of C
-    // of up to ~900 tiles; (3) the pipeline below otherwise (hub rows).  What a pair of operands turned out to need is remembered on A's
-    // handle, so that only the first product of a pair pays for a pass that did not fit (cage-like: 280 us).  BMSP_SPGEMM_ROWMERGE=0
-    // switches both off, =1 takes them under an explicit sort mode too, =2 skips strip mode.
-    // The memory records what the pair's STRUCTURE needs and nothing else (matrix.h, rm_partner_*): "strip mode does not fit" is written
-    // only by a strip pass that ran and overflowed, "it fits" only by one that ran and fitted; the list path (task-list mode, column
-    // windows, pipeline) is remembered beside it, not instead of it.  A product kept off strip mode by its arguments (the tc_version, a
-    // switch), by what the operands hold (values change) or by the predicates' refusal of a row-panel view says nothing about the pair:
-    // it neither replaces a remembered fit nor stands in for one -- the pair would stay off strip mode until a structure invalidate.
+    // the sort mode is left to the library.  (1) Strip mode -- one pass, no task list, numeric stage by a kernel that needs C's structure
+    // only -- when the rule names such a kernel (mac_choice.h) and every block-row of C holds at most mac_strip_row_cap() tiles; (2)
+    // task-list mode -- a count pass and a fill pass that also writes the sorted task list -- for block-rows of C of up to ~900 tiles;
+    // (3) the pipeline below otherwise (hub rows).  What a pair of operands turned out to need is remembered on A's handle, so that only
+    // the first product of a pair pays for a pass that did not fit (cage-like: 280 us).
+    // The memory records what the pair's STRUCTURE needs and nothing else (matrix.h, rm_partner_*): only a strip pass that ran writes
+    // "fits" or "does not fit".  MacPath::None -- the arguments, a switch, what the operands hold, a row-panel view -- runs no pass and
+    // writes nothing: it costs a few comparisons of cached figures and is asked again by the next product.
     uint64_t n_tasks = 0;
     uint32_t c_size = 0;
     DevBuf<uint64_t> k0, k1, v0, v1, rm_tasks;
@@ -1082,26 +1089,26 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
     const uint64_t *tasks_sorted = nullptr;
     bool have_tasks = false;
     {
-        const char *rme = getenv("BMSP_SPGEMM_ROWMERGE");
-        const bool rm_force = rme && rme[0] != '0', rm_off = rme && rme[0] == '0', rm_no_strip = rme && rme[0] == '2';
+        const PathSwitches ps = read_path_switches();
+        const bool rm_force = ps.rm_force, rm_off = ps.rm_off, win_off = ps.win_off, win_force = ps.win_force;
         const bool known = A->rm_partner_uid == B->uid;
         const int strip_fit = known ? A->rm_partner_strip : 0;  // 0 unknown, 1 strip mode fits, 2 a strip pass ran and did not fit
         const int hint = known ? A->rm_partner_mode : 0;        // the list path otherwise: 0 unknown, 2 task-list mode, 3 pipeline, 4 column windows
         auto remember_strip = [&](int fit) { rm_hint_key(A, B->uid); A->rm_partner_strip = fit; };
         auto remember_list = [&](int m) { rm_hint_key(A, B->uid); A->rm_partner_mode = m; };
-        // numeric stages that work from C's structure alone: the K = 32 MFMA strip kernel (tc_version 4, fp16) and its fp32 form (V15's
-        // summation order on v_mfma_f32_16x16x4_f32: any tc_version, as fp32 operands always take V15's numerics)
-        // ... and the row-sparse kernel: V15 numerics (fp32 operands, or fp16 under tc_version 5 -- the reference's default configuration) on
-        // operands of nearly empty tiles
-        const bool rm_numeric = (tc_version == 4 && mfma && !getenv("BMSP_MAC_OLD")) || (A->dtype == BMSP_F32 && !getenv("BMSP_MAC_VALU_DENSE") && !getenv("BMSP_MAC_F32MFMA")) ||
-                                (A->dtype == BMSP_F16 && tc_version == 5 && !getenv("BMSP_MAC_VALU_DENSE") && mac_rowsparse_applies(A, B, tc_version, st));
-        const char *sf = getenv("BMSP_MAC_STRIP");
-        // BMSP_SPGEMM_ROWWINDOW=0: never the column-window passes (rowwindow.hip); =1: always, whatever the operands look like (tests)
-        const char *we = getenv("BMSP_SPGEMM_ROWWINDOW");
-        const bool win_off = we && we[0] == '0', win_force = we && we[0] == '1';
-        const bool strip_allowed = rm_numeric && !rm_no_strip && !(sf && sf[0] == '0') && !win_force;
+        // strip mode's kernel, asked when a pass is about to run and not before (the rule may have to fetch value figures) -- except for
+        // fp16 under tc_version 5, which has always asked here: its value figures are fetched before T_2 whichever path follows
+        MacChoice strip_kernel;
+        bool strip_asked = false;
+        auto ask_strip_kernel = [&]() {
+            if (!strip_asked) strip_kernel = mac_decide(A, B, nullptr, nullptr, tc_version, sw, st);
+            strip_asked = true;
+            return strip_kernel.path != MacPath::None;
+        };
+        auto strip_allowed = [&]() { return !ps.strip_mode_off() && ask_strip_kernel(); };
+        if (A->dtype == BMSP_F16 && tc_version == 5) ask_strip_kernel();
         // strip mode done: value array, numeric stage (or zero values for bmsp_spgemm_symbolic), statistics
-        auto finish_strip = [&](uint64_t surv) {
+        auto finish_strip = [&](uint64_t surv, const MacChoice &kernel) {
             tm.mark(3);
             remember_strip(1);
             S->task_list_size = (int64_t)total;
@@ -1112,13 +1119,19 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
             finish_structure();
             tm.mark(9);
             if (C->block_num && !structure_only) {
-                S->mac_variant = launch_mac_strip(A, B, C.get(), tc_version, st);
-                S->mac_kernel = mfma ? tc_version : 5;
+                launch_block_mac(kernel, A, B, C.get(), nullptr, sw, S, st);
             } else if (C->nnz) {
                 BMSP_HIP(hipMemsetAsync(C->values, 0, dtype_size(C->dtype) * (size_t)C->nnz, st));  // bmsp_spgemm_symbolic: structure only
             }
             tm.mark(7);
             finish();
+        };
+        // after a pass: C is empty, or the kernel takes it (the capacity of a strip of C); otherwise C is dropped
+        auto strip_done = [&](uint64_t surv) {
+            const MacChoice kernel = C->block_num ? mac_decide(A, B, C.get(), nullptr, tc_version, sw, st) : strip_kernel;
+            if (kernel.path == MacPath::None) return false;
+            finish_strip(surv, kernel);
+            return true;
         };
         auto drop_structure = [&]() {
             pool_free(C->keys); pool_free(C->bmps); pool_free(C->rowptr); pool_free(C->offsets);
@@ -1131,16 +1144,13 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         // (also for a pair never seen whose row maxima bound every block-row of C by the strip kernel's capacity)
         const bool surely_fits = A->max_row_blocks >= 0 && B->max_row_blocks >= 0 &&
                                  (uint64_t)A->max_row_blocks * (uint64_t)B->max_row_blocks <= (uint64_t)mac_strip_row_cap();
-        if ((strip_fit == 1 || (strip_fit == 0 && surely_fits)) && n_a && strip_allowed && (mode == BMSP_SORT_AUTO || rm_force) && !rm_off &&
+        if ((strip_fit == 1 || (strip_fit == 0 && surely_fits)) && n_a && (mode == BMSP_SORT_AUTO || rm_force) && !rm_off &&
             (uint64_t)A->num_block_rows() * (uint64_t)mac_strip_row_cap() * 12 <= (4ull << 30) &&  // (beyond: T_2 first, scratch sized by the candidate pairs)
-            mac_structure_numeric_ok(A, B, tc_version, st)) {
+            strip_allowed()) {
             uint64_t surv = 0;
             strip_tried = true;
             if (rowmerge_symbolic(A, B, C.get(), nullptr, 0, mac_strip_row_cap(), &surv, &total, st)) {
-                if (C->block_num == 0 || mac_strip_fits_c(C.get(), st)) {
-                    finish_strip(surv);
-                    return;
-                }
+                if (strip_done(surv)) return;
                 drop_structure();
             }
             remember_strip(2);  // the pass ran and a block-row (or a strip) of C did not fit: the next product does not try it again
@@ -1148,21 +1158,12 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         }
         run_t2();
         const bool rm_on = !rm_off && total && (mode == BMSP_SORT_AUTO || rm_force);
-        // Strip mode is tried unless a pass is known to have overflowed.  Where the predicate refuses -- what the operands hold (the cached
-        // value figures: non-finite values, fp32 exponents outside the matrix pipe's range; values change: bmsp_matrix_invalidate(m, 0),
-        // copy / add / scale / sddmm into a handle), the tile fill under this tc_version, a row-panel view -- no pass runs and nothing is
-        // written about strip mode: the predicate costs a few comparisons of cached figures and is asked again by the next product, while
-        // a remembered refusal would keep the pair off strip mode for good.  Only a pass that ran and did not fit is remembered (hub
-        // block-rows): the first product of such a pair alone pays for it.
-        bool try_strip = rm_on && strip_allowed && !strip_tried && strip_fit != 2 && mac_structure_numeric_ok(A, B, tc_version, st);
+        // Strip mode is tried unless a pass is known to have overflowed (hub block-rows: the first product of such a pair alone pays for it)
+        const bool try_strip = rm_on && !strip_tried && strip_fit != 2 && strip_allowed();
         if (try_strip) {
             uint64_t surv = 0, cand = 0;
             if (rowmerge_symbolic(A, B, C.get(), first_pos.p, total, mac_strip_row_cap(), &surv, &cand, st)) {
-                if (C->block_num == 0 || mac_strip_fits_c(C.get(), st)) {
-                    finish_strip(surv);
-                    return;
-                }
-                // C exists but a strip of it exceeds the kernel's column list: drop it
+                if (strip_done(surv)) return;
                 drop_structure();
             }
             remember_strip(2);
@@ -1324,7 +1325,7 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
             C->sp_n_tasks = n_tasks; C->sp_candidates = total; C->sp_a_blocks = A->block_num; C->sp_b_blocks = B->block_num;
         }
     } else if (c_size) {
-        launch_block_mac(A, B, C.get(), tasks_sorted, n_tasks, task_begin.p, c_of_wave.p, total, tc_version, mfma, S, st);
+        block_mac_from_tasks(A, B, C.get(), MacTasks{tasks_sorted, n_tasks, total, task_begin.p, c_of_wave.p}, tc_version, sw, S, st);
     }
     tm.mark(7);
     finish();
@@ -1356,9 +1357,6 @@ void spgemm_numeric(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc
     bmsp_spgemm_stats local{};
     bmsp_spgemm_stats *S = stats ? stats : &local;
     *S = bmsp_spgemm_stats{};
-    const bool mfma = tc_version != 5 && A->dtype == BMSP_F16;
-    const bool strip_numeric = (tc_version == 4 && mfma && !getenv("BMSP_MAC_OLD")) || A->dtype == BMSP_F32 || (A->dtype == BMSP_F16 && tc_version == 5);
-    const char *sf = getenv("BMSP_MAC_STRIP");
     // The kernels below write C's values from the operands' structure and trust C to hold the product's: they run only for a C stamped
     // with THESE operands' fingerprints (a product of bmsp_spgemm / _symbolic on operands of the same structure).  A stamped C of other
     // operands is refused; an unstamped one (adopted arrays, a product of panel views) goes through the checked path at the end.
@@ -1368,29 +1366,29 @@ void spgemm_numeric(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, int tc
     // C is itself a valid left operand and may hold value-derived caches (CSR copy, lane / dense tiles, the finite flag) from a product it
     // took part in: every path below rewrites its values, so they go first, as for every other in-place writer
     drop_value_caches(C);
-    if (stamped && C->block_num && strip_numeric && !(sf && sf[0] == '0') && mac_structure_numeric_ok(A, B, tc_version, st) && mac_strip_fits_c(C, st)) {
-        StageTimer tm(st, true);
-        tm.mark(-1);
-        const int variant = launch_mac_strip(A, B, C, tc_version, st);
-        tm.mark(7);
-        BMSP_HIP(hipStreamSynchronize(st));
-        S->t_us[0] = tm.collect(S->t_us);
-        S->mac_variant = variant;
-        S->mac_kernel = mfma ? tc_version : 5;
-        S->c_blocks = C->block_num; S->c_nnz = C->nnz;
-        return;
-    }
-    if (stamped && C->block_num && C->sp_tasks && C->sp_a_blocks == A->block_num && C->sp_b_blocks == B->block_num) {
-        // C kept the product's sorted task list (bmsp_spgemm_symbolic): the block-MAC kernel of the tc_version runs from it
-        StageTimer tm(st, true);
-        tm.mark(-1);
-        launch_block_mac(A, B, C, C->sp_tasks, C->sp_n_tasks, C->sp_task_begin, C->sp_c_of_wave, C->sp_candidates, tc_version, mfma, S, st);
-        tm.mark(7);
-        BMSP_HIP(hipStreamSynchronize(st));
-        S->t_us[0] = tm.collect(S->t_us);
-        S->surviving_tasks = (int64_t)C->sp_n_tasks; S->task_list_size = (int64_t)C->sp_candidates;
-        S->c_blocks = C->block_num; S->c_nnz = C->nnz;
-        return;
+    // T_7 alone: from C's kept task list where strip mode is switched off (as bmsp_spgemm then decides), else by the kernel that needs
+    // C's structure only, else from the kept list
+    const bool stored = C->sp_tasks && C->sp_a_blocks == A->block_num && C->sp_b_blocks == B->block_num;
+    if (stamped && C->block_num) {
+        const MacSwitches sw = mac_read_switches();
+        const MacTasks tasks{C->sp_tasks, C->sp_n_tasks, C->sp_candidates, C->sp_task_begin, C->sp_c_of_wave};
+        MacChoice kernel;
+        if (!read_path_switches().strip_mode_off()) kernel = mac_decide(A, B, C, nullptr, tc_version, sw, st);
+        if (kernel.path != MacPath::None || stored) {
+            StageTimer tm(st, true);
+            tm.mark(-1);
+            if (kernel.path != MacPath::None) {
+                launch_block_mac(kernel, A, B, C, nullptr, sw, S, st);
+            } else {
+                block_mac_from_tasks(A, B, C, tasks, tc_version, sw, S, st);
+                S->surviving_tasks = (int64_t)C->sp_n_tasks; S->task_list_size = (int64_t)C->sp_candidates;
+            }
+            tm.mark(7);
+            BMSP_HIP(hipStreamSynchronize(st));
+            S->t_us[0] = tm.collect(S->t_us);
+            S->c_blocks = C->block_num; S->c_nnz = C->nnz;
+            return;
+        }
     }
     bmsp_matrix_s *full_raw = nullptr;
     spgemm(A, B, &full_raw, BMSP_SORT_AUTO, tc_version, 0, st, S);

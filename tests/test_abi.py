@@ -58,6 +58,14 @@ def test_host_bit_helpers_against_bruteforce(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
 
 
+def test_host_mac_choice_table(tmp_path):
+    """the block-MAC rule (csrc/mac_choice.h, no HIP) on both sides of every boundary, from facts built by hand"""
+    exe = str(tmp_path / "mac_choice")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", os.path.join(REPO, "tests", "host_mac_choice_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
+
+
 def _build_cpp_api_check(out_path):
     lib_dir = os.path.join(REPO, "bmsparse-spgemm-spmv_amd", "lib")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(REPO, "include"), os.path.join(REPO, "tests", "cpp_api_check.cpp"),

@@ -3,8 +3,8 @@ the generators, the table of cases and the CPU self-checks.  The GPU cases that 
 
 A.  The row-sparse block-MAC (blockmac_rowsparse.hip) multiplies from a CSR copy that rs_count_kernel / rs_fill_kernel build straight from
 the tiles: one wave per block-row, 64 tiles per step, the eight row counts of a step in 16-bit fields (four to a 64-bit word), a carry
-from step to step.  A block-row of 8192 tiles or more could overflow a field, so such a matrix has no copy (matrix.h kRsRowBlocksEnd)
-and mac_rowsparse_applies / prepare_spgemm_operand must ask before ensure_csr32 is reached.
+from step to step.  A block-row of 8192 tiles or more could overflow a field, so such a matrix has no copy (mac_choice.h kRsRowBlocksEnd)
+and the rule's per-operand half (mac_rowsparse_operand, asked for a product and by prepare_spgemm_operand) says so before ensure_csr32 is reached.
 
 steps             A: 11 block-rows of 0, 1, 63, 64, 65, 127, 128, 129, 191, 192, 193 tiles -- both sides of every 64-tile step and of every
                   carry; B: 193 block-rows whose lengths cycle through the same list inside 256 block columns (layout 1: the copy goes
@@ -36,9 +36,9 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "bmsparse-spgemm-spmv_amd", "csrc")
 
-RS_ROW_BLOCKS_END = 8192        # matrix.h kRsRowBlocksEnd: the first block-row length without a CSR copy
-RS_FILL_MAX = 16                # mac_rowsparse_applies / prepare_spgemm_operand: stored values per tile on average
-RS_C_ROW_MAX = 256              # strip mode's bound on a block-row of C (blockmac_rowsparse.hip rs_row_cap(9))
+RS_ROW_BLOCKS_END = 8192        # mac_choice.h kRsRowBlocksEnd: the first block-row length without a CSR copy
+RS_FILL_MAX = 16                # mac_choice.h kRsFillMax: stored values per tile on average, per operand
+RS_C_ROW_MAX = 256              # strip mode's bound on a block-row of C (mac_choice.h rs_row_cap(9))
 GROW_FACTOR, GROW_SLACK = 1.25, 1024    # comm.hip spgemm_sharded: nb_cap / nz_cap
 STEP_LENS = [0, 1, 63, 64, 65, 127, 128, 129, 191, 192, 193]
 HUB_LS = (8191, 8192, 8193)
@@ -50,19 +50,23 @@ def _src(name):
 
 
 def test_constants_match_sources():
-    """the limit is named once (matrix.h) and used by the gate, by prepare and by the guard; the fill rule; the sharded product's rule"""
-    m = re.findall(r"constexpr int64_t kRsRowBlocksEnd = 1 << (\d+);", _src("matrix.h"))
+    """the limit is named once (mac_choice.h) and used by the rule's per-operand half -- which the gate and prepare both ask -- and by the
+    guard; the fill rule; the sharded product's rule"""
+    rule = _src("mac_choice.h")
+    m = re.findall(r"constexpr int64_t kRsRowBlocksEnd = 1 << (\d+);", rule)
     assert len(m) == 1 and 1 << int(m[0]) == RS_ROW_BLOCKS_END
     rs, bld = _src("blockmac_rowsparse.hip"), _src("builder.hip")
-    assert re.search(r"A->max_row_blocks >= kRsRowBlocksEnd \|\| B->max_row_blocks >= kRsRowBlocksEnd\) return false;", rs)
+    assert len(re.findall(r"if \(m\.max_row_blocks >= kRsRowBlocksEnd\) return 0;", rule)) == 1
     assert re.search(r"if \(m->max_row_blocks >= kRsRowBlocksEnd\) fail\(BMSP_ERR_LIMIT", rs)
-    assert re.search(r"m->max_row_blocks < kRsRowBlocksEnd;", bld)
-    assert "1 << 13" not in rs and "1 << 13" not in bld
+    # the gate (mac_choose, through Eval::rowsparse) and prepare ask that half and spell no rule of their own
+    assert len(re.findall(r"mac_rowsparse_operand\(f\.a, f\.sw\) != 1 \|\| mac_rowsparse_operand\(f\.b, f\.sw\) != 1", rule)) == 1
+    assert re.search(r"const int rs = mac_rowsparse_operand\(m, sw\);", rule) and re.search(r"mac_prepare_forms\(mac_operand_facts\(m\)", bld)
+    assert "max_row_blocks" not in bld.split("void prepare_spgemm_operand")[1].split("\n}\n")[0]
+    assert "1 << 13" not in rs and "1 << 13" not in bld and rule.count("1 << 13") == 1
     # (a lane of rs_count_kernel, a step of rs_fill_kernel: 8 values per tile and row, fields of 16 bits)
     assert 8 * (RS_ROW_BLOCKS_END - 1) < 1 << 16 <= 8 * RS_ROW_BLOCKS_END
-    assert re.search(r"A->nnz <= %d \* A->block_num && B->nnz <= %d \* B->block_num" % (RS_FILL_MAX, RS_FILL_MAX), rs)
-    assert re.search(r"m->nnz <= %d \* m->block_num" % RS_FILL_MAX, bld)
-    assert re.search(r"rs_row_cap\(int hb\) \{ return hb == 9 \? %du" % RS_C_ROW_MAX, rs)
+    assert re.search(r"constexpr int64_t kRsFillMax = %d;" % RS_FILL_MAX, rule) and re.search(r"m\.nnz <= kRsFillMax \* m\.block_num", rule)
+    assert re.search(r"rs_row_cap\(int hb\) \{ return hb == 9 \? %du" % RS_C_ROW_MAX, rule)
     comm = _src("comm.hip")
     for res in ("b", "z"):
         m = re.search(r"n%s_cap = std::max<int64_t>\(need_%s, base_%s \+ \(int64_t\)\(\(double\)%s0\[\(size_t\)P\] \* left \* ([0-9.]+)\) \+ (\d+)\);" % (res, res, res, res), comm)

@@ -50,9 +50,9 @@ ROW_CAP = 384                 # rowmerge.hip kRowCap (strip mode is called with 
 HASH_BITS = 9                 # kHashBits: strip mode's table
 TL_CAP = 896                  # kTlCap
 TL_BITS = 10                  # kTlBits: task-list mode's table
-K_CAP = 192                   # blockmac_strip.hip kKCap: merged A tiles of a strip
+K_CAP = 192                   # mac_choice.h kKCap: merged A tiles of a strip (blockmac_strip.hip)
 J_CAP = 512                   # kJCap: merged C tiles of a strip
-RS_TABLE = 768                # blockmac_rowsparse.hip rs_row_cap(10)
+RS_TABLE = 768                # mac_choice.h rs_row_cap(10): the row-sparse kernel's larger table
 SMALL_PRODUCT = 2 << 20       # spgemm.hip small_product
 NARROW_CAP, WIDE_CAP = 2 * TASK_WAVE_MAX, TASK_WAVE_MAX   # a wave's capacity in sort words
 STRIP_ROW_CAP = J_CAP // 2
@@ -70,13 +70,13 @@ def test_constants_match_sources():
         m = [x for x in m if x]
         assert len(m) == 1, (name, len(m))
         return int(m[0].group(1))
-    seg, rm, strip = src("segsort.hip"), src("rowmerge.hip"), src("blockmac_strip.hip")
+    seg, rm, rule = src("segsort.hip"), src("rowmerge.hip"), src("mac_choice.h")    # (the capacities the block-MAC rule reads sit beside it)
     assert cx(seg, "kTaskWaveMax") == TASK_WAVE_MAX and cx(seg, "kBlockSegMax") == BLOCK_SEG_MAX
     assert cx(seg, "kTaskBlockIdxBits") == TASK_BLOCK_IDX_BITS and cx(seg, "kMergeTile") == MERGE_TILE
     assert cx(seg, "kSegRadixTile") == SEG_RADIX_TILE and cx(seg, "kSegRadixBits") == SEG_RADIX_BITS
     assert cx(rm, "kRowCap") == ROW_CAP and cx(rm, "kHashBits") == HASH_BITS and cx(rm, "kTlCap") == TL_CAP and cx(rm, "kTlBits") == TL_BITS
-    assert cx(strip, "kKCap") == K_CAP and cx(strip, "kJCap") == J_CAP
-    m = re.search(r"constexpr uint32_t rs_row_cap\(int hb\) \{ return hb == 9 \? (\d+)u : (\d+)u; \}", src("blockmac_rowsparse.hip"))
+    assert cx(rule, "kKCap") == K_CAP and cx(rule, "kJCap") == J_CAP
+    m = re.search(r"constexpr uint32_t rs_row_cap\(int hb\) \{ return hb == 9 \? (\d+)u : (\d+)u; \}", rule)
     assert m and int(m.group(1)) == STRIP_ROW_CAP and int(m.group(2)) == RS_TABLE
     m = re.search(r"small_product = total <= \((\d+)u << (\d+)\)", src("spgemm.hip"))
     assert m and int(m.group(1)) << int(m.group(2)) == SMALL_PRODUCT
@@ -392,6 +392,43 @@ def product(name, exact=False):
 
 def jbits_of(B):
     return max(1, int(B[1] // 8 - 1).bit_length())
+
+
+def tiny_product(kind):
+    """64 x 64 operands (8 x 8 tiles, every tile stored) for the cases that only ask WHICH block-MAC kernel runs: `sparse` -- two values per
+    tile, placed so that every candidate pair survives (A tile (i, k) holds a value in tile column k % 8, B tile (k, j) one in tile row
+    k % 8); `full` -- all 64 values; `tiny` -- `sparse` with the first stored value of either operand replaced by 2^-70 (their product is
+    no normal number).  Values are multiples of 1/4 up to 1 of both signs: fp16 holds them and every sum is exact in fp32 in any order."""
+    t = np.arange(64)
+    bi, bk = t // 8, t % 8
+    if kind == "full":
+        r = c = None
+        ra = rb = np.repeat(np.arange(64), 64)
+        ca = cb = np.tile(np.arange(64), 64)
+    else:
+        ra = np.concatenate([8 * bi + (bi + bk) % 8, 8 * bi + (bi + 2 * bk + 3) % 8])
+        ca = np.concatenate([8 * bk + bk % 8, 8 * bk + (bk + 4) % 8])
+        rb = np.concatenate([8 * bi + bi % 8, 8 * bi + (bi + 4) % 8])            # (B's tile (k, j) = (bi, bk) here)
+        cb = np.concatenate([8 * bk + (bi + bk) % 8, 8 * bk + (3 * bk + bi + 1) % 8])
+    va = ((ra * 3 + ca) % 4 + 1) / 4.0 * np.where((ra + ca // 3) % 2 == 0, 1.0, -1.0)
+    vb = ((rb + cb * 3) % 4 + 1) / 4.0 * np.where((rb // 2 + cb) % 2 == 0, 1.0, -1.0)
+    if kind == "tiny":
+        va[0] = vb[0] = 2.0 ** -70
+    return (64, 64, ra.astype(np.int64), ca.astype(np.int64), va), (64, 64, rb.astype(np.int64), cb.astype(np.int64), vb)
+
+
+def test_tiny_products_are_what_they_claim(oracle):
+    for kind, per_tile in (("sparse", 2), ("tiny", 2), ("full", 64)):
+        A, B = tiny_product(kind)
+        for M in (A, B):
+            key = (M[2] // 8) * 8 + M[3] // 8
+            assert np.unique(M[2] * 64 + M[3]).size == M[2].size and np.array_equal(np.bincount(key, minlength=64), np.full(64, per_tile))
+        _, st = oracle.spgemm(oracle.bmsp_from_coo(oracle.Coo(*A), 0, False), oracle.bmsp_from_coo(oracle.Coo(*B), 0, True))
+        assert st["task_list_size"] == st["surviving_tasks"] == 512 and st["c_blocks"] == 64     # every pair survives
+        assert 8 * 8 <= STRIP_ROW_CAP                                                            # ... and strip mode runs without T_2
+        mags = np.abs(np.concatenate([A[4], B[4]]))
+        assert np.array_equal(mags.astype(np.float16).astype(np.float64), mags) or kind == "tiny"
+        assert (mags.min() == 2.0 ** -70) == (kind == "tiny") and np.sort(mags)[2] >= 0.25 and mags.max() == 1.0
 
 
 def _oracle_product(oracle, name, dtype=0, exact=False):

@@ -7,7 +7,8 @@ The file is named to be collected last: every GPU test that was there before it 
 import numpy as np
 import pytest
 from test_gpu_parity import check_spgemm
-from test_spgemm_regimes import (NARROW_CAP, WIDE_CAP, BLOCK_SEG_MAX, TASK_BLOCK_IDX_BITS, STRIP_ROW_CAP, RS_TABLE, TL_CAP, product, product_terms, jbits_of)
+from test_spgemm_regimes import (NARROW_CAP, WIDE_CAP, BLOCK_SEG_MAX, TASK_BLOCK_IDX_BITS, STRIP_ROW_CAP, RS_TABLE, TL_CAP, product, product_terms, jbits_of,
+                                 tiny_product)
 
 _SWITCHES = ("BMSP_SPGEMM_ROWMERGE", "BMSP_SPGEMM_ROWWINDOW", "BMSP_SEGSORT_WIDE", "BMSP_SEGSORT_READBACK", "BMSP_SEGSORT_RADIX", "BMSP_SEGSORT_NO_MERGE",
              "BMSP_SEG_AVG_MAX", "BMSP_MAC_ROWSPARSE", "BMSP_MAC_STRIP", "BMSP_MAC_OLD", "BMSP_MAC_VALU_DENSE", "BMSP_MAC_F32MFMA", "BMSP_RM_BUILD_WAVE",
@@ -248,3 +249,66 @@ def test_d_expansion_tile(oracle, bmsp, monkeypatch, name):
     """D: exactly 2 << 20 candidate pairs (the small expansion tile) and one more (the large one)"""
     st = run(oracle, bmsp, monkeypatch, name, sort_env(), mode=1)
     assert st["sort_path"] == 1 and st["task_list_size"] == product(name)[2], st
+
+
+# name -> (operands of tiny_product, (dtype, tc_version), switches, B adopted with ownership 2, (mac_kernel, mac_variants allowed))
+_ONE_ANSWER = {
+    "f32_rowsparse": ("sparse", F32_V15, {}, False, (5, (5,))),
+    "f32_strip": ("sparse", F32_V15, {"BMSP_MAC_ROWSPARSE": "0"}, False, (5, (3,))),
+    "f32_tiny_values": ("tiny", F32_V15, {}, False, (5, (0,))),                      # products below 2^-126: the vector-ALU kernel
+    "f16_strip": ("full", F16_MFMA, {}, False, (4, (3,))),
+    "f16_k32_tasklist": ("full", F16_MFMA, {"BMSP_SPGEMM_ROWMERGE": "0"}, False, (4, (1, 2))),
+    "f16_k16": ("full", (1, 1), {}, False, (1, (0,))),
+    "f16_v15_rowsparse": ("sparse", F16_V15, {}, False, (5, (5,))),
+    "f64_valu": ("sparse", (2, 5), {}, False, (5, (0,))),
+    "f32_mfma_tasklist": ("full", F32_V15, {"BMSP_MAC_F32MFMA": "1"}, False, (5, (4,))),
+    "f32_adopted_b": ("sparse", F32_V15, {}, True, (5, (3,))),                       # no CSR copy of adopted arrays: never the row-sparse kernel
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(_ONE_ANSWER))
+def test_three_callers_one_answer(oracle, bmsp, monkeypatch, case):
+    """the block-MAC kernel is decided in one place (csrc/mac_choice.h): bmsp_spgemm, bmsp_spgemm_symbolic + bmsp_spgemm_numeric, and
+    bmsp_spgemm after bmsp_matrix_prepare(SPGEMM) on both operands -- each on handles of its own -- report the same mac_kernel and
+    mac_variant, the expected one, and store the oracle's values bit for bit (every sum of these operands is exact in fp32 in any order,
+    so the matrix cores' numerics have one answer too).  What prepare builds for an adopted operand is pinned by the host check of the
+    rule (tests/host_mac_choice_check.cpp): the handle does not show its cached forms."""
+    kind, (dtype, tc), env, adopt_b, (kernel, variants) = _ONE_ANSWER[case]
+    A, B = tiny_product(kind)
+    ref, rst = oracle.spgemm(oracle.bmsp_from_coo(oracle.Coo(*A), dtype, False), oracle.bmsp_from_coo(oracle.Coo(*B), dtype, True), exact_products=(dtype == 1 and tc != 5))
+    keep = []
+
+    def operands():
+        a, b = bmsp.BmSpMatrix.from_coo(*A, transposed=False, dtype=dtype), bmsp.BmSpMatrix.from_coo(*B, transposed=True, dtype=dtype)
+        if adopt_b:
+            keep.append(b)
+            b = bmsp.BmSpMatrix.from_device_arrays(B[0], B[1], *b.device_arrays(), dtype=dtype, transposed=True)
+        return a, b
+
+    with monkeypatch.context() as m:
+        for k in _SWITCHES + ("BMSP_MAC_B_DENSE", "BMSP_MAC_DIRECT"):
+            m.delenv(k, raising=False)
+        for k, v in env.items():
+            m.setenv(k, v)
+        a, b = operands()
+        whole = bmsp.spgemm(a, b, tc_version=tc)
+        a, b = operands()
+        split, _ = bmsp.spgemm_symbolic(a, b, tc_version=tc)
+        split = (split, bmsp.spgemm_numeric(a, b, split, tc_version=tc))
+        a, b = operands()
+        a.prepare(2)
+        b.prepare(2)
+        prepared = bmsp.spgemm(a, b, tc_version=tc)
+    answers = []
+    for what, (Cm, st) in (("bmsp_spgemm", whole), ("symbolic + numeric", split), ("prepare + bmsp_spgemm", prepared)):
+        print(case, what, {k: st[k] for k in ("sort_path", "sort_long", "mac_variant", "mac_kernel")})
+        k, bm, o, v = Cm.host_arrays()
+        np.testing.assert_array_equal(k, ref.keys)
+        np.testing.assert_array_equal(bm, ref.bmps)
+        np.testing.assert_array_equal(o, ref.offsets)
+        np.testing.assert_array_equal(v.astype(np.float64), ref.values, err_msg=what)
+        answers.append((st["mac_kernel"], st["mac_variant"]))
+    assert answers[0] == answers[1] == answers[2], answers
+    assert answers[0][0] == kernel and answers[0][1] in variants, answers
+    assert rst["surviving_tasks"] == 512 and whole[1]["surviving_tasks"] == 512 and whole[1]["c_nnz"] == ref.nnz
