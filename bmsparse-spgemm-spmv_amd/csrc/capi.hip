@@ -823,6 +823,27 @@ int bmsp_vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int 
     BMSP_API_END
 }
 
+int bmsp_matrix_aggregate(bmsp_matrix_t S, uint64_t seed, uint32_t *d_agg, int64_t *num_aggregates, void *stream, bmsp_aggregate_info *info)
+{
+    BMSP_API_BEGIN
+    need(S, "matrix S"); need(d_agg, "d_agg"); need(num_aggregates, "num_aggregates");
+    aggregate_check_matrix(S);
+    load_kernels();
+    aggregate(S, seed, d_agg, num_aggregates, as_stream(stream), info);
+    BMSP_API_END
+}
+
+int bmsp_matrix_from_aggregates(int num_rows, int num_aggregates, const uint32_t *d_agg, const void *d_weights, bmsp_dtype dtype,
+                                int transposed, void *stream, bmsp_matrix_t *out)
+{
+    BMSP_API_BEGIN
+    from_aggregates_check_args(num_rows, num_aggregates, d_agg, dtype, transposed);
+    need(out, "out");
+    load_kernels();
+    *out = matrix_from_aggregates(num_rows, num_aggregates, d_agg, d_weights, dtype, transposed, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *pc, const void *d_b, void *d_x, int64_t max_iter, double tol,
                       int flags, double *relres_history, bmsp_krylov_info *info, void *stream)
 {

@@ -290,6 +290,13 @@ void permute_check_matrix(const bmsp_matrix_s *A);
 bmsp_matrix_s *permute_blocks(bmsp_matrix_s *A, const uint32_t *d_row_perm, const uint32_t *d_col_perm, int out_transposed, hipStream_t st);
 void vec_permute_check_args(int64_t n, int vec_f64, const void *d_perm, int inverse, const void *d_x, const void *d_y);
 void vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int inverse, const void *d_x, void *d_y, hipStream_t st);
+// aggregate.hip: the MIS(2) aggregates of the scalar graph of a square S by hashed priorities (builds S's block-row pointer and op-T view
+// if they are missing; synchronises `st`); the num_rows x num_aggregates matrix with one entry (i, d_agg[i]) per row
+void aggregate_check_matrix(const bmsp_matrix_s *S);
+void aggregate(bmsp_matrix_s *S, uint64_t seed, uint32_t *d_agg, int64_t *num_aggregates, hipStream_t st, bmsp_aggregate_info *info);
+void from_aggregates_check_args(int num_rows, int num_aggregates, const uint32_t *d_agg, bmsp_dtype dtype, int transposed);
+bmsp_matrix_s *matrix_from_aggregates(int num_rows, int num_aggregates, const uint32_t *d_agg, const void *d_weights, bmsp_dtype dtype,
+                                      int transposed, hipStream_t st);
 // add.hip: C = alpha*A + beta*B with tiles in layout out_transposed; re-compute such a C's values from the same two structures
 bmsp_matrix_s *add_matrices(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, int out_transposed, hipStream_t st);
 void add_values(double alpha, bmsp_matrix_s *A, double beta, bmsp_matrix_s *B, bmsp_matrix_s *C, hipStream_t st);

@@ -51,7 +51,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -166,6 +166,16 @@ class ColorInfo(C.Structure):
         return d
 
 
+class AggregateInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("nodes", C.c_int64), ("aggregates", C.c_int64), ("rounds", C.c_int64), ("launches", C.c_int64),
+                ("view_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
 class Precond(C.Structure):
     _fields_ = [("kind", C.c_int), ("F", C.c_void_p), ("sweeps", C.c_int64)]
 
@@ -266,6 +276,8 @@ def lib():
         L.bmsp_matrix_color_blocks.argtypes = [vp, C.c_uint64, vp, vp, vp, p(ColorInfo)]
         L.bmsp_matrix_permute_blocks.argtypes = [vp, vp, vp, i, vp, p(vp)]
         L.bmsp_vec_permute_blocks.argtypes = [i64, i, vp, i, vp, vp, vp]
+        L.bmsp_matrix_aggregate.argtypes = [vp, C.c_uint64, vp, p(i64), vp, p(AggregateInfo)]
+        L.bmsp_matrix_from_aggregates.argtypes = [i, i, vp, vp, i, i, vp, p(vp)]
         L.bmsp_krylov_solve.argtypes =[vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
@@ -609,6 +621,15 @@ class BmSpMatrix:
         vec_permute_blocks takes"""
         _, perm, info = color_blocks(self, seed, stream)
         return permute_blocks(self, perm, perm, None, stream), perm, info
+
+    def aggregate(self, seed=0, stream=None):
+        """(agg, num_aggregates, info): the MIS(2) aggregates of this matrix's scalar graph: pybmsp.aggregate"""
+        return aggregate(self, seed, stream)
+
+    @staticmethod
+    def from_aggregates(agg, num_aggregates, weights=None, num_rows=None, dtype=F32, transposed=False, stream=None):
+        """the num_rows x num_aggregates matrix with weights[i] at (i, agg[i]): pybmsp.from_aggregates"""
+        return from_aggregates(agg, num_aggregates, weights, num_rows, dtype, transposed, stream)
 
     def mult_masked(self, B, M, alpha=1.0, beta=0.0, mul_m=False, transposed=None, stream=None):
         """alpha * (this * B) on M's pattern (+ beta * M, or * M) as a new matrix: pybmsp.spgemm_masked"""
@@ -1046,6 +1067,34 @@ def vec_permute_blocks(perm, x, inverse=False, y=None, n=None, stream=None):
         raise ValueError("perm must hold %d entries of uint32" % ((n + 7) // 8))
     check(lib().bmsp_vec_permute_blocks(n, f64, perm.ptr, int(inverse), x.ptr, y.ptr, stream))
     return y
+
+
+def aggregate(S, seed=0, stream=None):
+    """(agg, num_aggregates, info) of the MIS(2) aggregation of the scalar graph of a square S (bmsp_matrix_aggregate): any dtype, either
+    layout, structure only; rows i != j are neighbours iff (i, j) or (j, i) is stored.  agg: uint32 DeviceArray of num_rows entries, every
+    entry below num_aggregates, a pure function of structure and seed.  info = {"kernel", "nodes", "aggregates", "rounds", "launches",
+    "view_bytes"}.  Synchronises `stream`."""
+    agg = DeviceArray(S.info()["num_rows"], np.uint32)
+    count = C.c_int64()
+    info = AggregateInfo()
+    check(lib().bmsp_matrix_aggregate(S.h, int(seed) & 0xFFFFFFFFFFFFFFFF, agg.ptr, C.byref(count), stream, C.byref(info)))
+    return agg, count.value, info.as_dict()
+
+
+def from_aggregates(agg, num_aggregates, weights=None, num_rows=None, dtype=F32, transposed=False, stream=None):
+    """the num_rows x num_aggregates matrix (default: agg.n rows) with weights[i] (None: 1) stored at (i, agg[i]), one entry per row, its
+    tiles in layout `transposed` (bmsp_matrix_from_aggregates).  agg: uint32 DeviceArray, an entry 0xFFFFFFFF leaves its row empty, any
+    other entry must be below num_aggregates (checked on the device); weights: DeviceArray of float32 (float64 for F64).  Equals
+    from_coo_device on the same triples bit for bit.  Synchronises `stream`."""
+    nr = agg.n if num_rows is None else int(num_rows)
+    if agg.dtype != np.dtype(np.uint32) or agg.n < nr:
+        raise ValueError("agg must hold %d entries of uint32" % nr)
+    if weights is not None and (weights.dtype != np.dtype(OUT_DTYPE[dtype]) or weights.n < nr):
+        raise ValueError("weights must hold %d entries of %s" % (nr, np.dtype(OUT_DTYPE[dtype]).name))
+    h = C.c_void_p()
+    check(lib().bmsp_matrix_from_aggregates(nr, int(num_aggregates), agg.ptr, None if weights is None else weights.ptr, dtype,
+                                            int(bool(transposed)), stream, C.byref(h)))
+    return BmSpMatrix(h.value)
 
 
 def _precond(precond):

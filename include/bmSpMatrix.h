@@ -212,6 +212,20 @@ public:
         out.reset(t);
         return out;
     }
+    /* the num_rows x num_aggregates matrix with weights[i] (null: 1) stored at (i, agg[i]), one entry per row, agg[i] == 0xFFFFFFFF
+     * leaving row i empty (bmsp_matrix_from_aggregates): the tentative prolongator of an aggregate map; agg and weights are device
+     * arrays of num_rows entries, the weights float (double for double) */
+    static bmSpMatrix<valueType> from_aggregates(int num_rows, int num_aggregates, const uint32_t *agg,
+                                                 const typename bmsp::vector_of<valueType>::type *weights = nullptr,
+                                                 bool transposed_layout = false)
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_from_aggregates(num_rows, num_aggregates, agg, weights, bmsp::dtype_of<valueType>::value,
+                                                transposed_layout ? 1 : 0, nullptr, &t));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
     /* P * A * Q^T at tile granularity (bmsp_matrix_permute_blocks): block (I', J') of the result is block (row_perm[I'], col_perm[J'])
      * of this matrix; the permutations are device arrays of ceil(num_rows / 8) / ceil(num_cols / 8) entries, null = the identity */
     bmSpMatrix<valueType> permute_blocks(const uint32_t *row_perm, const uint32_t *col_perm, bool transposed_layout) const
@@ -418,6 +432,18 @@ inline void bmSparse_vec_permute_blocks(int64_t n, const uint32_t *perm, const R
     static_assert(sizeof(R) == 4 || sizeof(R) == 8, "float or double vectors");
     bmsp::check(bmsp_vec_permute_blocks(n, sizeof(R) == 8 ? 1 : 0, perm, inverse ? 1 : 0, x, y, nullptr));
     bmsp::check(bmsp_synchronize());
+}
+
+/* MIS(2) aggregation of the scalar graph of a square S by hashed priorities (bmsp_matrix_aggregate): agg is resized to num_rows and holds
+ * every row's aggregate; returns the number of aggregates.  Structure only: a pure function of S's pattern and the seed.  Synchronous. */
+template <class ValueIn>
+inline int64_t bmSparse_aggregate(bmSpMatrix<ValueIn> &S, bmsp::device_vector<uint32_t> &agg, uint64_t seed = 0,
+                                  bmsp_aggregate_info *info = nullptr)
+{
+    int64_t count = 0;
+    agg = bmsp::device_vector<uint32_t>((size_t)S.num_rows);
+    bmsp::check(bmsp_matrix_aggregate(S.handle(), seed, agg.data(), &count, nullptr, info));
+    return count;
 }
 
 /* Triangular solve for k right-hand sides (bmsp_spsm): op(tri(A)) * X = alpha * B; op, fill and diag as for bmSparse_SpSV.  B and X are

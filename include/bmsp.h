@@ -689,6 +689,65 @@ int bmsp_matrix_permute_blocks(bmsp_matrix_t A, const uint32_t *d_row_perm /* NU
                                const uint32_t *d_col_perm /* NULL = identity */, int out_transposed, void *stream, bmsp_matrix_t *out);
 int bmsp_vec_permute_blocks(int64_t n, int vec_f64, const uint32_t *d_perm, int inverse, const void *d_x, void *d_y, void *stream);
 
+/* Aggregation for algebraic multigrid on the device: the two stages of a smoothed-aggregation set-up that are neither a product, a sum,
+ * a scaling, a pruning nor a transpose -- partitioning the nodes of a strength graph into aggregates, and building the tentative
+ * prolongator from an aggregate map.  Nothing in the reference is replaced.
+ *
+ *   bmsp_matrix_aggregate: MIS(2) aggregates of the graph of a square S (any dtype, either layout).  Only S's structure is read: a stored
+ *       zero counts, values are never loaded; S and its caches are otherwise untouched.  d_agg holds n = num_rows entries of DEVICE memory.
+ *       Graph: the nodes are the scalar rows 0 .. n - 1 (not block-rows); i != j are neighbours iff (i, j) or (j, i) is stored.  The row
+ *           direction comes from S's keys, bitmaps and block-row pointer, the column direction from the cached op-T view of bmsp_spmv_op
+ *           (built if missing, which synchronises `stream`); S + S^T is not formed, so a strictly lower-triangular pattern aggregates
+ *           exactly like its symmetrisation.  Nothing is cached on the handle: the scratch is per call, from the pool.
+ *       Keys: key(i) = (splitmix64(seed ^ i) >> 32, i), compared lexicographically as unsigned (splitmix64 as for
+ *           bmsp_matrix_color_blocks above); the index half makes keys unique.
+ *       Roots: the maximal distance-2 independent set that the sequential greedy gives in descending key order -- i becomes a root iff
+ *           no node already chosen lies within distance <= 2 of it.  Distance is taken in the whole graph: a path through a decided node
+ *           counts.  The roots depend on nothing but structure and seed.
+ *       Aggregates: a root's id is its rank among the roots in ascending node index (one exclusive scan).  A non-root with a root among
+ *           its neighbours joins the neighbouring root of greatest key; every other node joins the root of greatest key among the roots
+ *           its neighbours are adjacent to (one exists, by maximality).  A node without neighbours is a root and a singleton.
+ *           *num_aggregates (host) is the number of roots; every d_agg[i] is below it.
+ *       Kernels (vector ALU; no floating-point atomic, no flag, no spin, no cooperative launch): one template, agg_pass_kernel, takes the
+ *           maximum of a per-node 8-byte word over the closed neighbourhood -- eight lanes per block-row, a lane per scalar row; the lanes
+ *           walk the block-row's tiles together, each taking its byte of every bitmap (layout 0) or its bit of every byte (layout 1),
+ *           then the view's records for the column direction the other way round; every set bit is one gather.  It serves the first- and
+ *           second-level passes of a round, the root-propagation pass and the final assignment, which propagates the greatest root key
+ *           instead of a flag.
+ *       Schedule: fixed-priority Luby rounds of TWO launches.  The first takes, for every node whatever its state, the greatest
+ *           undecided key in its closed neighbourhood, a root reading as "all ones".  The second, for every undecided node, takes the
+ *           maximum of those: all ones eliminates the node (a root within distance 2), its own key makes it a root, anything else leaves
+ *           it undecided.  Elimination therefore lags one round behind selection; this delays selections and never changes them.
+ *           `rounds` is the number of rounds that decided at least one node, which is every round run, the last one (eliminations
+ *           only) included.  BMSP_AGG_SCHEDULE=separate (a measurement switch, read per call) selects and eliminates in rounds of four
+ *           launches instead: the same roots and aggregates, another `rounds`; measured, it takes as many launches and as long.
+ *       Termination (bmsp_spitsv's protocol): every round records the nodes left undecided by integer atomics, one per workgroup; the
+ *           launches of the next round return at once when that is 0.  The host enqueues BMSP_AGG_CHECK rounds (default 8, at most 1024,
+ *           read per call) between read-backs; the switch never changes d_agg, *num_aggregates or `rounds`.
+ *       info (may be NULL): kernel = "agg_pass_kernel<layout 0>" / "<layout 1>" ("none (empty matrix)" for n = 0); nodes = n;
+ *           aggregates; rounds; launches = the kernels that did work (1 for the keys, 2 per round, the scan counted once, 2 for the
+ *           assignment); view_bytes = the op-T view's size.
+ *       Refused with BMSP_ERR_INVALID, the message naming the argument, nothing done on the device: null S, d_agg or num_aggregates; a
+ *       non-square S; a row-panel view.  BMSP_ERR_LIMIT: as for bmsp_spsv, and n beyond 2^32 - 2 (the node words).  Runs on `stream`
+ *       and synchronises it.
+ *
+ *   bmsp_matrix_from_aggregates: a fresh pool-owned num_rows x num_aggregates matrix P with P[i, d_agg[i]] = w_i, one stored entry per
+ *       row, tiles in layout `transposed`.  d_agg[i] == 0xFFFFFFFF leaves row i empty (how a caller drops nodes).  d_weights (NULL = ones)
+ *       has the vector type: float for BMSP_F16 / BMSP_F32, double for BMSP_F64, converted as the builder converts.  The four arrays and
+ *       the block-row pointer equal, bit for bit, what bmsp_matrix_from_coo_device builds from (i, d_agg[i], w_i) in that layout.
+ *       Construction, direct (no sort, no COO builder): per block-row eight lanes order their eight d_agg >> 3 inside the group and mark
+ *           the distinct ones; one scan of the packed (tiles, entries) counts gives the tile and value offsets; one pass writes keys,
+ *           bitmaps, offsets, values and the block-row pointer.  The builder orders tiles by (block-row, block-column) in both layouts
+ *           -- only the positions inside a tile differ -- so neither layout pays for a sort.
+ *       Checked on the device before anything is built (the flag comes back with the scan's totals in one 16-byte read-back): every entry
+ *       is below num_aggregates or the skip value; otherwise BMSP_ERR_INVALID naming d_agg, and *out is left untouched.  Also refused:
+ *       negative sizes; a null d_agg while num_rows > 0; a null out; `transposed` not 0 / 1; an unknown dtype.  Synchronises `stream`. */
+typedef struct { char kernel[64]; int64_t nodes, aggregates, rounds, launches, view_bytes; } bmsp_aggregate_info;
+int bmsp_matrix_aggregate(bmsp_matrix_t S, uint64_t seed, uint32_t *d_agg /* n entries, device */,
+                          int64_t *num_aggregates /* host */, void *stream, bmsp_aggregate_info *info /* may be NULL */);
+int bmsp_matrix_from_aggregates(int num_rows, int num_aggregates, const uint32_t *d_agg, const void *d_weights /* NULL = ones */,
+                                bmsp_dtype dtype, int transposed, void *stream, bmsp_matrix_t *out);
+
 /* Krylov solvers on the device: op(A) x = b for a square A in EITHER tile layout by preconditioned conjugate gradients (A symmetric
  * positive definite) or BiCGStab (van der Vorst's preconditioned form), with the whole iteration enqueued on `stream` -- products,
  * preconditioner, dot products, vector updates and the scalars alpha, beta, omega, which never leave the device.  Nothing in the reference
