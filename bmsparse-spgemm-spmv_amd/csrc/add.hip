@@ -228,7 +228,7 @@ bmsp_matrix_s *add_matrices(double alpha, bmsp_matrix_s *A, double beta, bmsp_ma
     m->nnz = A->nnz + (int64_t)(t >> 32);
     alloc_tile_arrays(m.get(), nc);
     alloc_values(m.get(), m->nnz);
-    m->add_map = (uint32_t *)pool_alloc(8 * (nc ? nc : 1));
+    m->add_map.alloc(2 * (size_t)(nc ? nc : 1));
     device_for_each(PlaceTiles{A->keys, B->keys, A->bmps, B->bmps, a_rank.p, b_rank.p, u.p, na, nc, a_flip, b_flip, m->keys, m->bmps, m->add_map},
                     na + nb, st);
     device_exclusive_scan<uint64_t>(CountIn{m->bmps, nc}, PtrOut<uint64_t>{m->offsets}, nc + 1, st);

@@ -420,7 +420,7 @@ bmsp_matrix_s *matrix_from_aggregates(int num_rows, int num_aggregates, const ui
     m->nnz = (int64_t)(h[0] & 0xffffffffull);
     alloc_tile_arrays(m.get(), (uint64_t)m->block_num);
     alloc_values(m.get(), (uint64_t)m->nnz);
-    m->rowptr = (uint32_t *)pool_alloc(sizeof(uint32_t) * (size_t)(nbr + 1));
+    m->rowptr.alloc((size_t)(nbr + 1));
     m->rowptr_rows = (int64_t)nbr;
     if (nbr == 0) {
         BMSP_HIP(hipMemsetAsync(m->offsets, 0, 8, st));

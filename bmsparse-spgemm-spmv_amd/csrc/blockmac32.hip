@@ -499,7 +499,7 @@ void ensure_dense_tiles(bmsp_matrix_s *m, hipStream_t st)
     // fp16: 128 B per block (the MFMA kernels' operand lines and the V15 staging); fp32: 256 B per block (V15 staging only)
     if (m->dtype != BMSP_F16 && m->dtype != BMSP_F32) fail(BMSP_ERR_INVALID, "dense tile copies exist for fp16 and fp32 matrices");
     const size_t es = dtype_size(m->dtype);
-    m->dense_tiles = pool_alloc(64 * es * (size_t)(m->block_num ? m->block_num : 1) + 64);
+    m->dense_tiles.alloc(64 * es * (size_t)(m->block_num ? m->block_num : 1) + 64);
     if (!m->block_num) return;
     if (m->dtype == BMSP_F16)
         device_for_each(ExpandDense<_Float16>{m->bmps, m->offsets, (const _Float16 *)m->values, (_Float16 *)m->dense_tiles}, (uint64_t)m->block_num * 64, st);

@@ -265,7 +265,7 @@ void ensure_lane_tiles(bmsp_matrix_s *m, hipStream_t st)
 {
     if (m->lane_tiles) return;
     if (m->dtype != BMSP_F32) fail(BMSP_ERR_INVALID, "lane-ordered tile copies exist for fp32 matrices");
-    m->lane_tiles = pool_alloc(256 * (size_t)(m->block_num ? m->block_num : 1) + 64);
+    m->lane_tiles.alloc(256 * (size_t)(m->block_num ? m->block_num : 1) + 64);
     if (m->block_num) device_for_each(ExpandLaneOrder{m->bmps, m->offsets, (const float *)m->values, (float *)m->lane_tiles}, (uint64_t)m->block_num * 64, st);
 }
 

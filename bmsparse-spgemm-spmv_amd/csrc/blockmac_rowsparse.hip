@@ -307,8 +307,8 @@ void ensure_csr32(bmsp_matrix_s *m, hipStream_t st)
     ensure_rowptr(m, st);
     ensure_row_stats(m, st);
     if (m->max_row_blocks >= kRsRowBlocksEnd) fail(BMSP_ERR_LIMIT, "row-sparse block-MAC: a block-row of 8192 or more tiles");  // (internal guard: the callers ask first)
-    m->csr_rowptr = (uint32_t *)pool_alloc(4 * ((size_t)rows + 1));
-    m->csr_ent = (uint32_t *)pool_alloc(8 * (size_t)(n ? n : 1));
+    m->csr_rowptr.alloc((size_t)rows + 1);
+    m->csr_ent.alloc(2 * (size_t)(n ? n : 1));
     const uint32_t nbr_c = (uint32_t)m->num_block_rows();
     if (nbr_c) {
         hipLaunchKernelGGL(rs_count_kernel, dim3((nbr_c + 3) / 4), dim3(kThreads), 0, st, (const uint64_t *)m->bmps, (const uint32_t *)m->rowptr, nbr_c, m->transposed, rows,

@@ -389,40 +389,7 @@ struct RowPtrSearch {
 void free_matrix(bmsp_matrix_s *m)
 {
     if (!m) return;
-    if (m->ownership == 1) {
-        pool_free(m->keys); pool_free(m->bmps); pool_free(m->offsets); pool_free(m->values);
-    }
-    pool_free(m->rowptr);
-    pool_free(m->spmv_chunks);
-    pool_free(m->spmv_pos);
-    pool_free(m->spmv_cw);
-    pool_free(m->block_meta);
-    pool_free(m->sym_recs);
-    pool_free(m->col_index); pool_free(m->col_index_row); pool_free(m->col_mass);
-    pool_free(m->dense_tiles);
-    pool_free(m->lane_tiles);
-    pool_free(m->csr_rowptr); pool_free(m->csr_ent);
-    pool_free(m->sp_tasks); pool_free(m->sp_task_begin); pool_free(m->sp_c_of_wave);
-    pool_free(m->tp_map);
-    pool_free(m->add_map);
-    drop_spmv_op_views(m);
-    drop_spsv_plans(m);
-    free_matrix(m->shard_view);
-    delete m;
-}
-
-void drop_spmv_op_views(bmsp_matrix_s *m)
-{
-    for (bmsp_spmv_op_view &w : m->spmv_op_views) {
-        pool_free(w.mem);
-        w = bmsp_spmv_op_view();
-    }
-    pool_free(m->spmv_op_tmp); m->spmv_op_tmp = nullptr;
-    pool_free(m->spmm_op_scratch); m->spmm_op_scratch = nullptr; m->spmm_op_scratch_elems = 0;
-    pool_free(m->spmm_op_tmp); m->spmm_op_tmp = nullptr; m->spmm_op_tmp_elems = 0;
-    pool_free(m->ilu0_diag); m->ilu0_diag = nullptr; m->ilu0_missing_row = -2;
-    pool_free(m->ilu0_tmp); m->ilu0_tmp = nullptr;
-    pool_free(m->krylov_ws); m->krylov_ws = nullptr; m->krylov_ws_bytes = 0;
+    delete m;  // every cache has an owner (matrix.h); the four arrays go with ownership 1
 }
 
 void alloc_tile_arrays(bmsp_matrix_s *m, uint64_t nb)
@@ -444,44 +411,21 @@ void refuse_view(const bmsp_matrix_s *m, const char *op)
     if (m->view_block_begin || m->view_values_end) fail(BMSP_ERR_INVALID, "%s: the matrix is a row-panel view; use the parent", op);
 }
 
-// Drops what the operators derived from the arrays and cached on the handle (bmsp_matrix_invalidate).  Value-derived: the dense tile
-// copies of the block-MAC kernels.  Structure-derived: block-row pointer and row maxima, SpMV plan and position cache, block records,
-// the sharded SpMV's panel view.  Everything is rebuilt lazily by the next operator call.
+// Drops what the operators derived from the arrays and cached on the handle (bmsp_matrix_invalidate): the value-derived group, and with
+// a changed structure the structure-derived group and the handle's uid (matrix.h).  Everything is rebuilt lazily by the next operator call.
 void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)
 {
     if (!m) return;
     BMSP_HIP(hipDeviceSynchronize());  // no kernel may still be reading what is about to go back to the pool
-    pool_free(m->dense_tiles); m->dense_tiles = nullptr;
-    pool_free(m->lane_tiles); m->lane_tiles = nullptr;
-    pool_free(m->csr_rowptr); pool_free(m->csr_ent);
-    m->csr_rowptr = nullptr; m->csr_ent = nullptr;
-    m->values_finite = -1;
-    if (!structure_changed) return;
-    pool_free(m->rowptr); m->rowptr = nullptr; m->rowptr_rows = 0; m->max_row_blocks = -1;
-    m->struct_hash = 0; m->sp_a_hash = 0; m->sp_b_hash = 0;
-    rm_hint_key(m, 0);
-    m->uid = next_matrix_uid();  // what other matrices remembered about this one's old structure no longer applies
-    pool_free(m->sp_tasks); pool_free(m->sp_task_begin); pool_free(m->sp_c_of_wave);
-    m->sp_tasks = nullptr; m->sp_task_begin = nullptr; m->sp_c_of_wave = nullptr; m->sp_n_tasks = 0;
-    pool_free(m->spmv_chunks); m->spmv_chunks = nullptr; m->spmv_num_chunks = 0; m->spmv_plan_long = 0; m->spmv_full_tiles = 0;
-    pool_free(m->spmv_pos); m->spmv_pos = nullptr; m->spmv_tinfo = nullptr; m->spmv_eoff = nullptr; m->spmv_pos_base = 0; m->spmv_pos_count = 0; m->spmv_pos_tried = 0;
-    pool_free(m->spmv_cw); m->spmv_cw = nullptr; m->spmv_cw_chunks = 0; m->spmv_cw_split = 0; m->spmv_cw_tried = 0; m->spmv_cw_layout = 0;
-    pool_free(m->block_meta); m->block_meta = nullptr;
-    pool_free(m->sym_recs); m->sym_recs = nullptr;
-    pool_free(m->col_index); pool_free(m->col_index_row); m->col_index = nullptr; m->col_index_row = nullptr; m->col_index_tried = 0;
-    pool_free(m->col_mass); m->col_mass = nullptr;
-    pool_free(m->tp_map); m->tp_map = nullptr; m->tp_src_uid = 0; m->tp_permute = 0;
-    pool_free(m->add_map); m->add_map = nullptr; m->add_a_uid = 0; m->add_b_uid = 0;
-    drop_spmv_op_views(m);
-    drop_spsv_plans(m);
-    free_matrix(m->shard_view); m->shard_view = nullptr; m->shard_world = 0; m->shard_rank = 0; m->shard_bounds.clear();
+    m->reset_value_caches();
+    if (structure_changed) m->reset_structure_caches();
 }
 
 // The value-derived caches of a matrix whose values an operation is about to rewrite (copy_values, add_values, scale_values) go as
 // bmsp_matrix_invalidate(m, 0) drops them; only a matrix that holds one pays for the device synchronisation.
 void drop_value_caches(bmsp_matrix_s *m)
 {
-    if (m->dense_tiles || m->lane_tiles || m->csr_rowptr || m->csr_ent) invalidate_matrix(m, 0);
+    if (m->holds_memory()) invalidate_matrix(m, 0);
     else m->values_finite = -1;
 }
 
@@ -490,7 +434,7 @@ void ensure_rowptr(bmsp_matrix_s *m, hipStream_t st)
     if (m->rowptr) return;
     int64_t nbr = m->num_block_rows();
     if (m->block_num >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "more than 2^32 blocks");
-    m->rowptr = (uint32_t *)pool_alloc(sizeof(uint32_t) * (size_t)(nbr + 1));
+    m->rowptr.alloc((size_t)(nbr + 1));
     m->rowptr_rows = nbr;
     device_for_each(RowPtrSearch{m->keys, (uint32_t)m->block_num, m->rowptr}, (uint64_t)nbr + 1, st);
 }
@@ -564,7 +508,7 @@ void ensure_block_meta(bmsp_matrix_s *m, hipStream_t st)
 {
     if (m->block_meta) return;
     if ((uint64_t)m->values_extent() >= (1ull << 32)) fail(BMSP_ERR_LIMIT, "packed block records hold 32-bit value offsets");
-    m->block_meta = (uint32_t *)pool_alloc(16 * (size_t)(m->block_num ? m->block_num : 1));
+    m->block_meta.alloc(4 * (size_t)(m->block_num ? m->block_num : 1));
     if (m->block_num) device_for_each(PackBlockMeta{m->bmps, m->offsets, m->block_meta}, (uint64_t)m->block_num, st);
 }
 
@@ -604,7 +548,7 @@ __global__ __launch_bounds__(kThreads) void tile_product_selftest_kernel(uint32_
 void ensure_sym_recs(bmsp_matrix_s *m, hipStream_t st)
 {
     if (m->sym_recs) return;
-    m->sym_recs = (uint32_t *)pool_alloc(16 * (size_t)(m->block_num ? m->block_num : 1));
+    m->sym_recs.alloc(4 * (size_t)(m->block_num ? m->block_num : 1));
     if (m->block_num) device_for_each(PackSymRecs{m->keys, m->bmps, m->sym_recs}, (uint64_t)m->block_num, st);
 }
 
@@ -655,8 +599,7 @@ struct FillColIndex {
 void ensure_col_index(bmsp_matrix_s *m, uint32_t gran, hipStream_t st)
 {
     if (m->col_index_tried && m->col_index_gran == gran) return;
-    pool_free(m->col_index); pool_free(m->col_index_row);
-    m->col_index = nullptr; m->col_index_row = nullptr;
+    m->col_index.release(); m->col_index_row.release();
     m->col_index_tried = 1; m->col_index_gran = gran;
     ensure_rowptr(m, st);
     const uint64_t rows = (uint64_t)m->num_block_rows();
@@ -667,8 +610,8 @@ void ensure_col_index(bmsp_matrix_s *m, uint32_t gran, hipStream_t st)
     device_exclusive_scan<uint64_t>(IdxEntriesIn{m->rowptr, rows, (uint32_t)per_row}, IdxRowOut{m->rowptr, idx_row.p, rows, total_h.dev()}, rows + 1, st);
     const uint64_t total = total_h.wait(st);
     if (total * 4 > (256ull << 20)) return;
-    m->col_index = (uint32_t *)pool_alloc(4 * (size_t)(total ? total : 1));
-    m->col_index_row = idx_row.take();
+    m->col_index.alloc((size_t)total);
+    m->col_index_row = std::move(idx_row);
     if (total) device_for_each(FillColIndex{m->keys, m->rowptr, m->col_index_row, m->col_index, (uint32_t)per_row, gran}, rows * per_row, st);
 }
 
@@ -709,7 +652,7 @@ void ensure_col_mass(bmsp_matrix_s *m, uint32_t gran, hipStream_t st)
         hipLaunchKernelGGL(mass_count_kernel, dim3(grid), dim3(kThreads), 0, st, m->keys, (uint64_t)m->block_num, gran, (uint32_t)G, hist.p);
         BMSP_CHECK_LAUNCH();
     }
-    m->col_mass = (uint32_t *)pool_alloc(4 * (size_t)(G + 1));
+    m->col_mass.alloc((size_t)(G + 1));
     device_exclusive_scan<uint32_t>(PtrIn<uint32_t>{hist.p}, PtrOut<uint32_t>{m->col_mass}, G + 1, st);
 }
 

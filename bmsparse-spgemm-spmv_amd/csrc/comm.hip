@@ -409,7 +409,7 @@ void spgemm_sharded(bmsp_comm_s *c, bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_mat
                 }
                 if (base_z) BMSP_HIP(hipMemcpyAsync(nv, C->values, es * (size_t)base_z, hipMemcpyDeviceToDevice, st));
                 BMSP_HIP(hipStreamSynchronize(st));
-                pool_free(C->keys); pool_free(C->bmps); pool_free(C->offsets); pool_free(C->values);
+                C->release_arrays();
                 C->keys = nk; C->bmps = nbm; C->offsets = no; C->values = nv;
                 cap_b = nb_cap; cap_z = nz_cap;
             }
@@ -499,12 +499,11 @@ void spmv_sharded(bmsp_comm_s *c, bmsp_matrix_s *A, const void *x, void *y, int 
     const size_t es = A->dtype == BMSP_F64 ? 8 : 4;
     // the panel view (with its cached sweep plan) is kept on the matrix for repeated products with the same communicator shape
     if (!A->shard_view || A->shard_world != P || A->shard_rank != c->rank) {
-        free_matrix(A->shard_view);
-        A->shard_view = nullptr;
+        A->shard_view.reset();
         std::vector<int64_t> bounds;
         spmv_bounds(A, P, bounds, st);
         A->shard_bounds.assign(bounds.begin(), bounds.end());
-        A->shard_view = row_panel(A, bounds[(size_t)c->rank], bounds[(size_t)c->rank + 1], st);
+        A->shard_view = own_matrix(row_panel(A, bounds[(size_t)c->rank], bounds[(size_t)c->rank + 1], st));
         A->shard_world = P; A->shard_rank = c->rank;
     }
     std::vector<int64_t> cnt((size_t)P), start((size_t)P);
@@ -526,7 +525,7 @@ void spmv_sharded(bmsp_comm_s *c, bmsp_matrix_s *A, const void *x, void *y, int 
         }
     } else {
         const int r = c->rank;
-        spmv(A->shard_view, x, y, variant, st, start[(size_t)r], start[(size_t)r] + cnt[(size_t)r]);
+        spmv(A->shard_view.get(), x, y, variant, st, start[(size_t)r], start[(size_t)r] + cnt[(size_t)r]);
         src[(size_t)r] = (const char *)y + es * (size_t)start[(size_t)r];
     }
     StageTimer tm(st, sh != nullptr);

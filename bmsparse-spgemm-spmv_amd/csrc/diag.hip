@@ -258,7 +258,7 @@ bmsp_matrix_s *matrix_from_diagonal(int num_rows, int num_cols, const void *d_di
     const uint64_t nbr = (uint64_t)m->num_block_rows();
     alloc_tile_arrays(m.get(), nt);
     alloc_values(m.get(), n);
-    m->rowptr = (uint32_t *)pool_alloc(sizeof(uint32_t) * (size_t)(nbr + 1));
+    m->rowptr.alloc((size_t)(nbr + 1));
     m->rowptr_rows = (int64_t)nbr;
     const uint64_t work = n > nbr + 1 ? n : nbr + 1;  // (nt <= nbr)
     dispatch_dtype(dtype, [&](auto s) {

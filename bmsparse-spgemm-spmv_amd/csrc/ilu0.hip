@@ -207,13 +207,12 @@ const bmsp_spmv_op_view &ensure_buffers(bmsp_matrix_s *F, hipStream_t st)
         BMSP_HIP(hipStreamSynchronize(st));
         uint32_t first = ~0u;
         copy_d2h_staged(&first, missing.p, 4);
-        pool_free(F->ilu0_diag);
-        F->ilu0_diag = diag.take();
+        F->ilu0_diag = std::move(diag);
         F->ilu0_missing_row = first == ~0u ? -1 : (int64_t)first;
     }
     if (F->ilu0_missing_row >= 0)
         fail(BMSP_ERR_INVALID, "matrix A: row %lld of A has no stored diagonal entry", (long long)F->ilu0_missing_row);
-    if (!F->ilu0_tmp) F->ilu0_tmp = pool_alloc(dtype_size(F->dtype) * (size_t)F->nnz);
+    if (!F->ilu0_tmp) F->ilu0_tmp.alloc(dtype_size(F->dtype) * (size_t)F->nnz);
     return w;
 }
 

@@ -442,10 +442,9 @@ void run_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, con
     const size_t need = off_rec + (checked ? sizeof(KrylovRecord) * (size_t)m : 0);
     if (need > A->krylov_ws_bytes) {
         if (A->krylov_ws) BMSP_HIP(hipStreamSynchronize(st));  // (work enqueued on the old one has finished before it goes back to the pool)
-        pool_free(A->krylov_ws);
-        A->krylov_ws = nullptr;
+        A->krylov_ws.release();
         A->krylov_ws_bytes = 0;
-        A->krylov_ws = pool_alloc(need);
+        A->krylov_ws.alloc(need);
         A->krylov_ws_bytes = need;
     }
     char *ws = (char *)A->krylov_ws;

@@ -6,16 +6,22 @@
 #include "mac_choice.h"
 #include "runtime.h"
 #include <memory>
+#include <utility>
 #include <vector>
 
-namespace bmsp { uint64_t next_matrix_uid(); }
+struct bmsp_matrix_s;
+namespace bmsp {
+uint64_t next_matrix_uid();
+// a matrix under construction, a view made per call, or one kept by another handle: freed with everything it holds unless released
+using MatrixPtr = std::unique_ptr<bmsp_matrix_s>;
+}  // namespace bmsp
 
 // The cached view of bmsp_spmv_op for one op (spmv_op.hip): the tiles as 16-byte records {bitmap lo, hi, value offset, the tile's OTHER
 // block index} in the order the sweep walks them, the pointer of blocks + 1 entries per output block (op T; op N uses rowptr), the work
 // items {output block, first tile, end tile, scratch slot or ~0u}, the fold list {output block, first slot, parts} of the split blocks and
 // 8 accumulators of scratch per slot -- one allocation, structure only (kept across value-only invalidation).
 struct bmsp_spmv_op_view {
-    uint32_t *mem = nullptr;
+    bmsp::DevBuf<uint32_t> mem;
     size_t off_ptr = 0, off_items = 0, off_folds = 0, off_scratch = 0, bytes = 0;
     int64_t blocks = 0, items = 0, split_blocks = 0, slots = 0;
 };
@@ -25,38 +31,40 @@ struct bmsp_spmv_op_view {
 // level kernel, 1 one chain kernel)}, three words per launch.  missing_diag_row: the first row below n whose diagonal entry A does not
 // store (-1: none) -- what a BMSP_DIAG_NON_UNIT call is refused for.
 struct bmsp_spsv_plan_s {
-    uint32_t *mem = nullptr;
+    bmsp::DevBuf<uint32_t> mem;
     size_t off_level_ptr = 0, bytes = 0;
     int64_t blocks = 0, levels = 0, max_level_width = 0, chain_launches = 0, chained_levels = 0, chain = 0, missing_diag_row = -1;
     std::vector<uint32_t> level_ptr, segments;
 };
 
-struct bmsp_matrix_s {
-    // identity of this matrix's STRUCTURE: a fresh number at construction and after bmsp_matrix_invalidate(m, 1).  What one matrix remembers
-    // about another (the row-merge hint below) is keyed by it -- not by a device pointer, which the pool hands out again
-    uint64_t uid = bmsp::next_matrix_uid();
-    int num_rows = 0, num_cols = 0;
-    int64_t nnz = 0, block_num = 0;
-    bmsp_dtype dtype = BMSP_F32;
-    int transposed = 0;
-    // the four public arrays of the reference container (device memory)
-    uint64_t *keys = nullptr;     // block_num
-    uint64_t *bmps = nullptr;     // block_num
-    uint64_t *offsets = nullptr;  // block_num + 1 (last = nnz)
-    void *values = nullptr;       // nnz elements of dtype
-    int ownership = 1;            // 1: arrays belong to the pool / this handle, 2: borrowed
-    // derived, built lazily and cached (never part of the reference's public state)
-    uint32_t *rowptr = nullptr;   // dense block-row pointer, num_block_rows()+1 entries
+// What the operators derive from a handle's four arrays and cache on it is built lazily, is never part of the reference's public state, and
+// lives in two groups.  Every member's initialiser is its "not built" value and every allocation has an owner, so a group is dropped by
+// assigning a fresh one (bmsp_matrix_s::reset_*): a new cache needs its line here and nowhere else.
+
+// Derived from the VALUES (and the structure): dropped by bmsp_matrix_invalidate(m, 0) and before an operation rewrites the values in place.
+struct bmsp_value_caches {
+    // fp16 matrices: every tile expanded to 64 halves in position order (128 B per block), for the K = 32 MFMA block-MAC: built lazily
+    bmsp::DevBuf<void> dense_tiles;
+    bmsp::DevBuf<uint32_t> csr_rowptr, csr_ent;  // fp32 operands of the row-sparse block-MAC: a row-major CSR copy (row pointer of num_rows + 1 entries; {column, value bits} per stored value)
+    bmsp::DevBuf<void> lane_tiles;   // fp32 matrices: tiles in the lane order of the fp32 MFMA block-MAC (256 B per block): built lazily
+    int values_finite = -1;          // fp16 operands of the strip block-MAC: 1 = no inf / NaN stored (-1 = not looked yet)
+    int f32_exp_min = 255, f32_exp_max = 0;  // fp32: biased exponent range of the non-zero stored values (with values_finite)
+    bool holds_memory() const { return dense_tiles || lane_tiles || csr_rowptr || csr_ent; }
+};
+
+// Derived from the STRUCTURE alone (keys, bitmaps, offsets): kept across value-only invalidation, dropped by bmsp_matrix_invalidate(m, 1).
+struct bmsp_structure_caches {
+    bmsp::DevBuf<uint32_t> rowptr;  // dense block-row pointer, num_block_rows()+1 entries
     int64_t rowptr_rows = 0;
     int64_t max_row_blocks = -1;  // most blocks in one block-row (ensure_row_stats; bounds the SpGEMM's task segments without a read-back)
     // sweep plan of the SpMV (see spmv.hip): chunk descriptors
-    uint32_t *spmv_chunks = nullptr;
+    bmsp::DevBuf<uint32_t> spmv_chunks;
     int64_t spmv_num_chunks = 0;
     int64_t spmv_plan_long = 0;
     int64_t spmv_full_tiles = 0;  // tiles with all 64 values stored (decides the sweep variant)
     size_t spmv_plan_off_cnt = 0, spmv_plan_off_carry = 0;
     // position cache of the value-stream SpMV: one 16-bit {tile slot in its batch, position in the tile} entry per stored value
-    uint16_t *spmv_pos = nullptr;
+    bmsp::DevBuf<uint16_t> spmv_pos;
     uint32_t *spmv_tinfo = nullptr;  // same allocation: per tile {block column, block-row inside its item's window} (the value-stream kernel's slot word)
     uint16_t *spmv_eoff = nullptr;   // same allocation: per tile, end of its values relative to its item's first value
     int64_t spmv_pos_base = 0, spmv_pos_count = 0;
@@ -64,23 +72,19 @@ struct bmsp_matrix_s {
     // chunked sweep (spmv_chunk_kernel): one 32-bit word {row relative to the chunk's first block-row, column} per stored value, padded to
     // whole chunks | chunk records | arrival counters | carry slots -- one allocation, structure only (kept across value-only invalidation).
     // spmv_cw_layout: 1 = the words in storage order (round 7), 2 = row-sorted words {column, storage index, run start, window bitmap bits}
-    uint32_t *spmv_cw = nullptr;
+    bmsp::DevBuf<uint32_t> spmv_cw;
     int64_t spmv_cw_chunks = 0, spmv_cw_split = 0;  // chunks; block-rows folded across chunks
     size_t spmv_cw_off_rec = 0, spmv_cw_off_cnt = 0, spmv_cw_off_carry = 0;
     int spmv_cw_colbits = 0, spmv_cw_tried = 0, spmv_cw_layout = 0;
     // (bitmap, value offset) of every block as one 16-byte record, for kernels that gather both (block-MAC): built lazily
-    uint32_t *block_meta = nullptr;  // block_num x {bmp lo, bmp hi, offset in elements, 0}
-    uint32_t *sym_recs = nullptr;    // right operands: block_num x {bitmap ROW-major (lo, hi), block column, rows the tile uses}: all the column-window passes (rowwindow.hip) read per candidate pair
+    bmsp::DevBuf<uint32_t> block_meta;  // block_num x {bmp lo, bmp hi, offset in elements, 0}
+    bmsp::DevBuf<uint32_t> sym_recs;    // right operands: block_num x {bitmap ROW-major (lo, hi), block column, rows the tile uses}: all the column-window passes (rowwindow.hip) read per candidate pair
     // column index of the long block-rows (right operands of the column-window passes): col_index[col_index_row[k] + c / col_index_gran] = first
     // tile of block-row k whose block column is >= c; col_index_row[k] = ~0 for block-rows of at most kIdxMinLen tiles
-    uint32_t *col_mass = nullptr;  // prefix sums of this matrix's tiles per granule of col_index_gran block columns (ceil(cols / gran) + 1 entries): where the column-window passes cut
-    uint32_t *col_index = nullptr, *col_index_row = nullptr;
+    bmsp::DevBuf<uint32_t> col_mass;  // prefix sums of this matrix's tiles per granule of col_index_gran block columns (ceil(cols / gran) + 1 entries): where the column-window passes cut
+    bmsp::DevBuf<uint32_t> col_index, col_index_row;
     uint32_t col_index_gran = 0;
     int col_index_tried = 0;
-    // fp16 matrices: every tile expanded to 64 halves in position order (128 B per block), for the K = 32 MFMA block-MAC: built lazily
-    void *dense_tiles = nullptr;
-    uint32_t *csr_rowptr = nullptr, *csr_ent = nullptr;  // fp32 operands of the row-sparse block-MAC: a row-major CSR copy (row pointer of num_rows + 1 entries; {column, value bits} per stored value)
-    void *lane_tiles = nullptr;   // fp32 matrices: tiles in the lane order of the fp32 MFMA block-MAC (256 B per block): built lazily
     // SpGEMM row-merge paths: what the product of this matrix with the right operand whose uid is rm_partner_uid (B's uid: the key of the
     // three fields below) turned out to need, so that the next product of the pair goes there directly.  The memory holds only what the
     // pair's STRUCTURE needs, two facts kept apart: whether strip mode fits (rm_partner_strip: 0 unknown, 1 a strip pass ran and fitted,
@@ -92,8 +96,8 @@ struct bmsp_matrix_s {
     int rm_partner_mode = 0;
     int64_t rm_partner_cw_hash = 0;  // column-window passes: candidate pairs per hashed window that worked for the pair (0: the default)
     // a product made by bmsp_spgemm_symbolic keeps its sorted task list for bmsp_spgemm_numeric (T_7 alone on new operand values)
-    uint64_t *sp_tasks = nullptr;
-    uint32_t *sp_task_begin = nullptr, *sp_c_of_wave = nullptr;
+    bmsp::DevBuf<uint64_t> sp_tasks;
+    bmsp::DevBuf<uint32_t> sp_task_begin, sp_c_of_wave;
     uint64_t sp_n_tasks = 0, sp_candidates = 0;
     int64_t sp_a_blocks = 0, sp_b_blocks = 0;
     // a product remembers which operand STRUCTURES it was formed from (struct_hash of A and B; 0 = not stamped: a view, adopted arrays): the
@@ -102,45 +106,73 @@ struct bmsp_matrix_s {
     // made by bmsp_matrix_transpose / bmsp_matrix_convert_layout / bmsp_matrix_scale: the source's uid (0 = neither), the source tile of every tile (the sort's
     // payload; null = the source's tile order) and whether values are permuted inside each tile -- what bmsp_matrix_copy_values replays
     uint64_t tp_src_uid = 0;
-    uint32_t *tp_map = nullptr;
+    bmsp::DevBuf<uint32_t> tp_map;
     int tp_permute = 0;
     // made by bmsp_matrix_add: the operands' uids (0 = not a sum) and, per tile, its A tile (add_map[c]) and its B tile (add_map[block_num + c];
     // ~0u = none) -- what bmsp_matrix_add_values replays
     uint64_t add_a_uid = 0, add_b_uid = 0;
-    uint32_t *add_map = nullptr;
+    bmsp::DevBuf<uint32_t> add_map;
     uint64_t struct_hash = 0;  // this matrix: sum over its blocks of mix(key, bitmap), + dimensions; 0 = not computed (ensure_struct_hash)
-    int values_finite = -1;
-    int f32_exp_min = 255, f32_exp_max = 0;  // fp32: biased exponent range of the non-zero stored values (with values_finite)       // fp16 operands of the strip block-MAC: 1 = no inf / NaN stored (-1 = not looked yet)
     // bmsp_spmv_op: the view per op (0 = N, 1 = T), built on first use; the sum of a layout-0 matrix under op N before its epilogue
     bmsp_spmv_op_view spmv_op_views[2];
-    void *spmv_op_tmp = nullptr;
+    bmsp::DevBuf<void> spmv_op_tmp;
     // bmsp_spmm_op (spmm_op.hip): 8 * k accumulators per scratch slot of the views' split blocks, and the sum of a layout-0 matrix under
-    // op N before its epilogue; both grow to the largest call seen and go with the views (drop_spmv_op_views)
-    void *spmm_op_scratch = nullptr, *spmm_op_tmp = nullptr;
+    // op N before its epilogue; both grow to the largest call seen
+    bmsp::DevBuf<void> spmm_op_scratch, spmm_op_tmp;
     int64_t spmm_op_scratch_elems = 0, spmm_op_tmp_elems = 0;
-    // bmsp_spsv: the plan per [op][fill], built by bmsp_spsv_analyse or the first solve; goes with the views (structure changes, free)
+    // bmsp_spsv: the plan per [op][fill], built by bmsp_spsv_analyse or the first solve
     bmsp_spsv_plan_s spsv_plans[2][2];
-    // bmsp_spitsv: the second iterate buffer, num_rows vector elements, made by the first call; goes with the plans (one stream per handle
-    // at a time: two calls on two streams would share it)
-    void *spitsv_tmp = nullptr;
-    // bmsp_matrix_ilu0 (ilu0.hip), on the factor F: the value index of every (j, j), num_rows entries, structure only; the first row
-    // whose diagonal entry is not stored (-1: none; -2: not looked yet); the second iterate buffer, nnz storage elements.  They go with
-    // the op-T view the sweeps walk (drop_spmv_op_views); one stream per handle at a time, as for spitsv_tmp.
-    uint32_t *ilu0_diag = nullptr;
+    // bmsp_spitsv: the second iterate buffer, num_rows vector elements, made by the first call (one stream per handle at a time: two calls
+    // on two streams would share it)
+    bmsp::DevBuf<void> spitsv_tmp;
+    // bmsp_matrix_ilu0 (ilu0.hip), on the factor F: the value index of every (j, j), num_rows entries; the first row whose diagonal entry
+    // is not stored (-1: none; -2: not looked yet); the second iterate buffer, nnz storage elements.  One stream per handle at a time, as
+    // for spitsv_tmp.
+    bmsp::DevBuf<uint32_t> ilu0_diag;
     int64_t ilu0_missing_row = -2;
-    void *ilu0_tmp = nullptr;
+    bmsp::DevBuf<void> ilu0_tmp;
     // bmsp_krylov_solve (krylov.hip), on A: one allocation -- scalars and ticket | dot partials | diagonal | vectors | records -- sized
-    // for the largest need seen; goes with the views (drop_spmv_op_views); one stream per handle at a time
-    void *krylov_ws = nullptr;
+    // for the largest need seen; one stream per handle at a time
+    bmsp::DevBuf<void> krylov_ws;
     size_t krylov_ws_bytes = 0;
-    // a row-panel view points into its parent
-    int64_t view_block_begin = 0;
     // sharded SpMV (comm.hip): this rank's panel view, kept for its cached sweep plan
-    bmsp_matrix_s *shard_view = nullptr;
+    bmsp::MatrixPtr shard_view;
     int shard_world = 0, shard_rank = 0;
     std::vector<int64_t> shard_bounds;
+};
 
+struct bmsp_matrix_s : bmsp_value_caches, bmsp_structure_caches {
+    // identity of this matrix's STRUCTURE: a fresh number at construction and after bmsp_matrix_invalidate(m, 1).  What one matrix remembers
+    // about another (the row-merge hint above) is keyed by it -- not by a device pointer, which the pool hands out again
+    uint64_t uid = bmsp::next_matrix_uid();
+    int num_rows = 0, num_cols = 0;
+    int64_t nnz = 0, block_num = 0;
+    bmsp_dtype dtype = BMSP_F32;
+    int transposed = 0;
+    // the four public arrays of the reference container (device memory): raw, because the ABI hands them out and `ownership` decides them
+    uint64_t *keys = nullptr;     // block_num
+    uint64_t *bmps = nullptr;     // block_num
+    uint64_t *offsets = nullptr;  // block_num + 1 (last = nnz)
+    void *values = nullptr;       // nnz elements of dtype
+    int ownership = 1;            // 1: arrays belong to the pool / this handle, 2: borrowed
+    // a row-panel view points into its parent
+    int64_t view_block_begin = 0;
     int64_t view_values_end = 0;  // row-panel views: end (in elements) of the panel's values inside the parent's array
+
+    // the four arrays go back to the pool if they are this handle's (ownership 1), and are forgotten either way
+    void release_arrays()
+    {
+        if (ownership == 1) { bmsp::pool_free(keys); bmsp::pool_free(bmps); bmsp::pool_free(offsets); bmsp::pool_free(values); }
+        keys = bmps = offsets = nullptr; values = nullptr;
+    }
+    ~bmsp_matrix_s() { release_arrays(); }
+    // what invalidate_matrix does to the handle once the device is idle (no HIP call here: tests/host_handle_check.cpp runs these)
+    void reset_value_caches() { static_cast<bmsp_value_caches &>(*this) = bmsp_value_caches(); }
+    void reset_structure_caches()
+    {
+        static_cast<bmsp_structure_caches &>(*this) = bmsp_structure_caches();
+        uid = bmsp::next_matrix_uid();  // what other matrices remembered about this one's old structure no longer applies
+    }
     // elements addressable from `values`: offsets of a view stay absolute into the parent's value array
     int64_t values_extent() const { return view_values_end ? view_values_end : nnz; }
     int64_t num_block_rows() const { return ((int64_t)num_rows + 7) / 8; }
@@ -250,9 +282,7 @@ void matrix_compare_device(bmsp_matrix_s *m, int64_t nnz, const int *d_rows, con
 bmsp_matrix_s *build_from_device_csr(int num_rows, int num_cols, int64_t nnz, const int *d_row_offsets, const int *d_cols, const double *d_vals,
                                      int transposed, bmsp_dtype dtype, hipStream_t st);
 void free_matrix(bmsp_matrix_s *m);
-// a matrix under construction (or a view made per call): freed with everything it holds unless released to the caller
-using MatrixPtr = std::unique_ptr<bmsp_matrix_s, void (*)(bmsp_matrix_s *)>;
-inline MatrixPtr own_matrix(bmsp_matrix_s *m) { return MatrixPtr(m, free_matrix); }
+inline MatrixPtr own_matrix(bmsp_matrix_s *m) { return MatrixPtr(m); }
 inline MatrixPtr make_matrix() { return own_matrix(new bmsp_matrix_s()); }
 // pooled arrays of a matrix of nb tiles / nnz elements of m->dtype, never empty allocations (at least one element each).
 // alloc_tile_arrays makes whichever of keys, bmps (nb) and offsets (nb + 1) the matrix does not hold yet; the values are a call of
@@ -265,14 +295,14 @@ void refuse_view(const bmsp_matrix_s *m, const char *op);
 // before m's values are rewritten in place: drops what invalidate_matrix(m, 0) drops
 void drop_value_caches(bmsp_matrix_s *m);
 // transpose.hip: the tiles of a matrix in (block-column, block-row) order -- the sorted swapped keys and, as payload, the source tile of
-// each.  The four buffers live as long as the struct (the pool is not stream-aware); take_* hands the two results to a matrix.
+// each.  The four buffers live as long as the struct (the pool is not stream-aware); take_* hands the two results to a matrix (the keys raw: a public array).
 struct TileSort {
     DevBuf<uint64_t> k0, k1;
     DevBuf<uint32_t> p0, p1;
     const uint64_t *keys = nullptr;
     const uint32_t *map = nullptr;
     uint64_t *take_keys() { return keys == k0.p ? k0.take() : k1.take(); }
-    uint32_t *take_map() { return map == p0.p ? p0.take() : p1.take(); }
+    DevBuf<uint32_t> take_map() { return std::move(map == p0.p ? p0 : p1); }
 };
 void sort_tiles_by_block_column(const bmsp_matrix_s *A, TileSort &ts, hipStream_t st);
 // transpose.hip: out = A^T (swap) or A (!swap) with tiles in layout out_transposed; re-gather such an out's values from A
@@ -339,7 +369,6 @@ void spsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const void
 void spsv_analyse(bmsp_matrix_s *A, int op, int fill, int diag, hipStream_t st, bmsp_spsv_info *info);
 void spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments);
-void drop_spsv_plans(bmsp_matrix_s *m);
 // spsm.hip: the triangular solve for k right-hand sides, op(tri(A)) * X = alpha * B, on the plan of spsv.hip (built if it is missing,
 // which synchronises `st`); what that call launches
 void spsm_check_args(int op, int fill, int diag, int k, int64_t ldb, int64_t ldx);
@@ -384,7 +413,6 @@ void spmv_op(bmsp_matrix_s *A, int op, double alpha, const void *v, double beta,
 void spmv_op_launch_info(bmsp_matrix_s *A, int op, hipStream_t st, bmsp_spmv_op_info *info);
 void spmv_op_plan_items(const uint32_t *ptr, int64_t blocks, int64_t split, uint32_t *items, uint32_t *folds, int64_t *n_items,
                         int64_t *split_blocks, int64_t *slots);
-void drop_spmv_op_views(bmsp_matrix_s *m);
 // what bmsp_spmm_op shares with bmsp_spmv_op: the argument checks (`what` names the call in the messages), the lengths of op(A)'s input and
 // output, the element size of the vectors that go with A, the cached view of (A, op) -- built if it is missing, which synchronises `st`
 // -- and the epilogue

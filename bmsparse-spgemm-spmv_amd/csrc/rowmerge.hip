@@ -889,7 +889,7 @@ bool rowmerge_symbolic(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, con
         return false;
     }
     C->block_num = c_size;
-    C->rowptr = c_rowptr;
+    C->rowptr.adopt(c_rowptr);
     C->rowptr_rows = (int64_t)rows;
     C->max_row_blocks = (int64_t)(uint32_t)mo;
     alloc_tile_arrays(C, (uint64_t)c_size);
@@ -982,7 +982,7 @@ bool rowmerge_tasklist(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, con
         return false;
     }
     C->block_num = c_size;
-    C->rowptr = c_rowptr;
+    C->rowptr.adopt(c_rowptr);
     C->rowptr_rows = (int64_t)rows;
     C->max_row_blocks = (int64_t)(uint32_t)mo;
     alloc_tile_arrays(C, (uint64_t)c_size);

@@ -742,7 +742,7 @@ bool rowmerge_windowed(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s *C, con
     const uint32_t c_size = c_size_h.wait(st), n_tasks = n_tasks_h.wait(st);
     const uint64_t c_nnz = nnz_h.wait(st);
     C->block_num = c_size;
-    C->rowptr = (uint32_t *)pool_alloc(sizeof(uint32_t) * (size_t)(rows + 1));
+    C->rowptr.alloc((size_t)(rows + 1));
     C->rowptr_rows = (int64_t)rows;
     C->max_row_blocks = -1;  // (ensure_row_stats looks when somebody asks)
     alloc_tile_arrays(C, (uint64_t)c_size);

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include "../../include/bmsp.h"
 
 namespace bmsp {
@@ -45,8 +46,11 @@ void pool_free(void *p);
 void pool_trim();
 bool pool_owns(void *p);
 
+// A pooled allocation and its owner: move-only, back to the pool on destruction and on re-assignment.  Temporaries of a call and the
+// caches of a matrix handle (matrix.h) are both held this way; a DevBuf<void> counts bytes.
 template <typename T>
 struct DevBuf {
+    using Elem = std::conditional_t<std::is_void<T>::value, char, T>;
     T *p = nullptr;
     size_t n = 0;
     DevBuf() = default;
@@ -64,7 +68,14 @@ struct DevBuf {
     {
         release();
         n = count;
-        p = static_cast<T *>(pool_alloc((count ? count : 1) * sizeof(T)));
+        p = static_cast<T *>(pool_alloc((count ? count : 1) * sizeof(Elem)));
+    }
+    // takes over an allocation of the pool made elsewhere (size() says `count`, not what the pool holds)
+    void adopt(T *q, size_t count = 0)
+    {
+        release();
+        p = q;
+        n = count;
     }
     void release()
     {
@@ -80,6 +91,10 @@ struct DevBuf {
         return q;
     }
     T *data() const { return p; }
+    // readers spell a held buffer like the pointer: kernel arguments, arithmetic, null tests, and casts to another element type
+    operator T *() const { return p; }
+    template <typename U>
+    explicit operator U *() const { return (U *)p; }
     size_t size() const { return n; }
 };
 

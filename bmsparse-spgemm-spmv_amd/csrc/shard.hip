@@ -75,16 +75,16 @@ bmsp_matrix_s *row_panel(bmsp_matrix_s *m, int64_t rb, int64_t re, hipStream_t s
     ensure_rowptr(m, st);
     uint32_t b0 = read_back(m->rowptr + rb, st), b1 = read_back(m->rowptr + re, st);
     uint64_t o0 = read_back(m->offsets + b0, st), o1 = read_back(m->offsets + b1, st);
-    bmsp_matrix_s *v = new bmsp_matrix_s();
+    auto v = make_matrix();
     v->num_rows = m->num_rows; v->num_cols = m->num_cols; v->dtype = m->dtype; v->transposed = m->transposed;
     v->block_num = (int64_t)(b1 - b0);
     v->nnz = (int64_t)(o1 - o0);
+    v->ownership = 2;
     v->keys = m->keys + b0; v->bmps = m->bmps + b0; v->offsets = m->offsets + b0;
     v->values = m->values;  // offsets stay absolute into the parent's value array
-    v->ownership = 2;
     v->view_block_begin = b0;
     v->view_values_end = (int64_t)o1;
-    return v;
+    return v.release();
 }
 
 bmsp_matrix_s *concat_panels(int num_rows, int num_cols, int parts, const int64_t *block_nums, const int64_t *nnzs,
@@ -97,12 +97,12 @@ bmsp_matrix_s *concat_panels(int num_rows, int num_cols, int parts, const int64_
         nb += block_nums[p];
         nz += nnzs[p];
     }
-    bmsp_matrix_s *m = new bmsp_matrix_s();
+    auto m = make_matrix();
     m->num_rows = num_rows; m->num_cols = num_cols; m->dtype = dtype; m->transposed = 0;
     m->block_num = nb; m->nnz = nz;
     const size_t es = dtype_size(dtype);
-    alloc_tile_arrays(m, (uint64_t)nb);
-    alloc_values(m, (uint64_t)nz);
+    alloc_tile_arrays(m.get(), (uint64_t)nb);
+    alloc_values(m.get(), (uint64_t)nz);
     int64_t bb = 0, zz = 0;
     for (int p = 0; p < parts; p++) {
         size_t cb = (size_t)block_nums[p], cz = (size_t)nnzs[p];
@@ -119,7 +119,7 @@ bmsp_matrix_s *concat_panels(int num_rows, int num_cols, int parts, const int64_
     uint64_t term = (uint64_t)nz;
     BMSP_HIP(hipMemcpyAsync(m->offsets + nb, &term, 8, hipMemcpyHostToDevice, st));
     BMSP_HIP(hipStreamSynchronize(st));
-    return m;
+    return m.release();
 }
 
 // One GPU, a product whose candidate block pairs exceed the 32-bit task range: the same row-panel decomposition the multi-GPU path

@@ -1134,8 +1134,8 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
             return true;
         };
         auto drop_structure = [&]() {
-            pool_free(C->keys); pool_free(C->bmps); pool_free(C->rowptr); pool_free(C->offsets);
-            C->keys = nullptr; C->bmps = nullptr; C->rowptr = nullptr; C->offsets = nullptr; C->nnz = 0;
+            C->release_arrays();  // (no values yet: finish_structure makes them)
+            C->rowptr.release(); C->nnz = 0;
             C->rowptr_rows = 0; C->max_row_blocks = -1; C->block_num = 0;
         };
         bool strip_tried = false;
@@ -1319,9 +1319,9 @@ void spgemm(bmsp_matrix_s *A, bmsp_matrix_s *B, bmsp_matrix_s **Cout, int mode, 
         // bmsp_spgemm_symbolic: zero values, and C keeps the sorted task list so that bmsp_spgemm_numeric can run T_7 alone from it
         if (C->nnz) BMSP_HIP(hipMemsetAsync(C->values, 0, dtype_size(C->dtype) * (size_t)C->nnz, st));
         if (c_size && n_tasks) {
-            C->sp_tasks = have_tasks ? rm_tasks.take() : (tasks_sorted == v0.p ? v0.take() : v1.take());
-            C->sp_task_begin = task_begin.take();
-            C->sp_c_of_wave = c_of_wave.take();
+            C->sp_tasks = std::move(have_tasks ? rm_tasks : (tasks_sorted == v0.p ? v0 : v1));
+            C->sp_task_begin = std::move(task_begin);
+            C->sp_c_of_wave = std::move(c_of_wave);
             C->sp_n_tasks = n_tasks; C->sp_candidates = total; C->sp_a_blocks = A->block_num; C->sp_b_blocks = B->block_num;
         }
     } else if (c_size) {

@@ -148,7 +148,7 @@ void spitsv(bmsp_matrix_s *A, int op, int fill, int diag, double alpha, const vo
     const bmsp_spmv_op_view *w = view_of(A, op, st, &ptr);  // (both exist: the plan was made from them)
     const SweepArgs args{A, tiles_of(A, w), ptr, pl.blocks, alpha, stats ? tol : 0.0, b};
     const size_t bytes = spmv_op_vector_size(A) * (size_t)A->num_rows;
-    if (!A->spitsv_tmp) A->spitsv_tmp = pool_alloc(bytes);
+    if (!A->spitsv_tmp) A->spitsv_tmp.alloc(bytes);
     // x^j lives in even(j) ? first : second.  A given x^0 is d_x's content; otherwise x^0 = +0 is written into the temporary, d_x is not
     // read and the first sweep overwrites it.
     void *first = x, *second = A->spitsv_tmp;

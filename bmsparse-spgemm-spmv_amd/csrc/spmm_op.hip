@@ -165,13 +165,12 @@ int64_t scratch_elems(const bmsp_spmv_op_view &w, int k)
 }
 
 // a buffer on the handle that only grows; growing waits for the work enqueued on the old one
-void grow(void *&buf, int64_t &have, int64_t need, size_t elem, hipStream_t st)
+void grow(DevBuf<void> &buf, int64_t &have, int64_t need, size_t elem, hipStream_t st)
 {
     if (need <= have && buf) return;
     if (buf) BMSP_HIP(hipStreamSynchronize(st));
-    pool_free(buf);
-    buf = nullptr; have = 0;
-    buf = pool_alloc(elem * (size_t)(need ? need : 1));
+    buf.release(); have = 0;
+    buf.alloc(elem * (size_t)(need ? need : 1));
     have = need;
 }
 

@@ -152,7 +152,7 @@ void build_plan(bmsp_matrix_s *A, hipStream_t st)
     uint32_t hdr[4] = {n_items, n_long, (uint32_t)off_cnt, (uint32_t)off_carry};
     BMSP_HIP(hipMemcpyAsync(mem, hdr, sizeof hdr, hipMemcpyHostToDevice, st));
     if (nbr) device_exclusive_scan<uint64_t>(rc, PlanFill{rc, nb, (SweepItem *)(mem + off_items)}, (uint64_t)nbr + 1, st);
-    A->spmv_chunks = (uint32_t *)mem;
+    A->spmv_chunks.adopt((uint32_t *)mem);
     A->spmv_num_chunks = n_items;
     A->spmv_plan_long = n_long;
     A->spmv_plan_off_cnt = off_cnt;
@@ -901,7 +901,7 @@ void build_pos_cache(bmsp_matrix_s *A, hipStream_t st)
                        A->bmps, A->offsets, (const float *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, (uint32_t *)nullptr,
                        (uint32_t)A->num_rows, (uint32_t)A->num_cols, 0u, pos, (uint32_t)base, (uint32_t)count, 0u, A->spmv_tinfo, A->spmv_eoff);
     BMSP_CHECK_LAUNCH();
-    A->spmv_pos = pos;
+    A->spmv_pos.adopt(pos);
     A->spmv_pos_base = (int64_t)base;
     A->spmv_pos_count = (int64_t)count;
 }
@@ -1575,7 +1575,7 @@ void build_chunk_cache(bmsp_matrix_s *A, hipStream_t st)
         }
         BMSP_HIP(hipStreamSynchronize(st));  // the host records and the staging buffer go away with this scope
     }
-    A->spmv_cw = (uint32_t *)mem;
+    A->spmv_cw.adopt((uint32_t *)mem);
     A->spmv_cw_layout = sorted ? 2 : 1;
     A->spmv_cw_chunks = nch;
     A->spmv_cw_split = split;

@@ -210,8 +210,8 @@ bmsp_spmv_op_view &spmv_op_ensure_view(bmsp_matrix_s *A, int op, hipStream_t st)
     BMSP_HIP(hipStreamSynchronize(st));  // the sort temporaries go back to the pool
     copy_h2d_staged(mem.p + nw.off_items, items.data(), 4 * items.size());
     copy_h2d_staged(mem.p + nw.off_folds, folds.data(), 4 * folds.size());
-    nw.mem = (uint32_t *)mem.take();
-    w = nw;
+    nw.mem.adopt((uint32_t *)mem.take());
+    w = std::move(nw);
     return w;
 }
 
@@ -266,7 +266,7 @@ void spmv_plain(bmsp_matrix_s *A, double alpha, const void *v, double beta, void
         spmv(A, v, u, BMSP_SPMV_DEFAULT, st);
         return;
     }
-    if (!A->spmv_op_tmp) A->spmv_op_tmp = pool_alloc(spmv_op_vector_size(A) * (size_t)(A->num_rows ? A->num_rows : 1));
+    if (!A->spmv_op_tmp) A->spmv_op_tmp.alloc(spmv_op_vector_size(A) * (size_t)(A->num_rows ? A->num_rows : 1));
     spmv(A, v, A->spmv_op_tmp, BMSP_SPMV_DEFAULT, st);
     if (f64) launch_epilogue<double>(A->spmv_op_tmp, alpha, beta, u, A->num_rows, st);
     else launch_epilogue<float>(A->spmv_op_tmp, alpha, beta, u, A->num_rows, st);

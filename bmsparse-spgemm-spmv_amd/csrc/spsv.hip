@@ -112,17 +112,6 @@ void spsv_check_matrix(const bmsp_matrix_s *A)
     spmv_op_check_matrix(A, "spsv");
 }
 
-void drop_spsv_plans(bmsp_matrix_s *m)
-{
-    for (auto &per_op : m->spsv_plans)
-        for (bmsp_spsv_plan_s &pl : per_op) {
-            pool_free(pl.mem);
-            pl = bmsp_spsv_plan_s();
-        }
-    pool_free(m->spitsv_tmp);
-    m->spitsv_tmp = nullptr;
-}
-
 // Levels and launch schedule of a substitution over `blocks` output blocks whose records [ptr[I], ptr[I + 1]) carry the other block
 // index other[t]: block I depends on every other[t] < I (lower) or > I (upper).  Host only.
 void spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,

@@ -233,7 +233,7 @@ inline bmsp_spsv_plan_s &ensure_plan(bmsp_matrix_s *A, int op, int fill, hipStre
     DevBuf<char> mem(np.bytes);
     if (blocks) copy_h2d_staged(mem.p, order.data(), 4 * (size_t)blocks);
     copy_h2d_staged(mem.p + np.off_level_ptr, np.level_ptr.data(), 4 * ((size_t)n_levels + 1));
-    np.mem = (uint32_t *)mem.take();
+    np.mem.adopt((uint32_t *)mem.take());
     pl = std::move(np);
     return pl;
 }

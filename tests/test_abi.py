@@ -66,6 +66,21 @@ def test_host_mac_choice_table(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
 
 
+def test_host_handle_lifetimes(tmp_path):
+    """what a handle caches (csrc/matrix.h, no HIP linked) against a counting pool: the two resets of bmsp_matrix_invalidate, re-assigned
+    owners, delete with either ownership, buffers moved out; and the program filled as many owners as the struct declares"""
+    from test_structure_invalidate import scan_handle
+    exe = str(tmp_path / "handle")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                           os.path.join(REPO, "tests", "host_handle_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
+    owning = scan_handle()[0]
+    allocations = sum({"spmv_op_views": 2, "spsv_plans": 4, "shard_view": 0}.get(f, 1) for f in owning)
+    assert out.stdout.split() == ["OK", "owners=%d" % allocations], (out.stdout, sorted(owning))
+
+
 def _build_cpp_api_check(out_path):
     lib_dir = os.path.join(REPO, "bmsparse-spgemm-spmv_amd", "lib")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(REPO, "include"), os.path.join(REPO, "tests", "cpp_api_check.cpp"),

@@ -1,9 +1,10 @@
 """bmsp_matrix_invalidate(m, 1) against every structure-derived cache of a handle.
 
 include/bmsp.h lets a caller rewrite `keys`, `bmps` and `offsets` of a handle in place and call bmsp_matrix_invalidate(m, 1); from then
-on every operator must see the new structure.  The promise rests on one hand-kept list, invalidate_matrix in csrc/builder.hip (and the two
-drop_* functions it calls).  A cache that is missing from the list produces no error: the next call succeeds with the numbers of the old
-structure.  One GPU case (tests/test_zzzzzzzz_structure_invalidate.py) is: build A from a pattern P, prepare(3), make ONE call pinned to
+on every operator must see the new structure.  The promise rests on csrc/matrix.h: every structure-derived cache is a member of
+bmsp_structure_caches, which owns its allocations and which invalidate_matrix (csrc/builder.hip) replaces by a fresh one.  A cache kept
+anywhere else produces no error: the next call succeeds with the numbers of the old structure (section 5 and tests/host_handle_check.cpp
+guard the rule, the GPU cases its effect).  One GPU case (tests/test_zzzzzzzz_structure_invalidate.py) is: build A from a pattern P, prepare(3), make ONE call pinned to
 one kernel or route and assert from launch info / stats that it ran (the cache exists) and gave P's result; write P' over A's four arrays
 (from a second handle built from P' by from_coo, through bmsp_memcpy_h2d), A.invalidate(True); the same call on A and on `fresh`, a handle
 built from P', must agree bit for bit with each other and with the reference (numpy float64 on P''s COO; the oracle for products; the
@@ -396,7 +397,7 @@ def _spmv_ids(prefix):
 
 
 OTHER_FILES = "tests/"      # a case id that starts with this names a test of another file: "tests/<file>::<test function>"
-# every pooled field of bmsp_matrix_s that bmsp_matrix_invalidate(m, 1) must release -> the GPU cases that read it after a rewrite
+# every owning member of the handle's two cache groups (bmsp_matrix_invalidate(m, 1) releases them all) -> the GPU cases that read it after a rewrite
 CACHES = {
     "rowptr": _ids("rowptr_reader") + _spmv_ids("spmv_blockrow_kernel") + _spmv_ids("spmv_rowgroup_kernel") + _ids("spgemm_route", lambda p: p[1] == "right_rowptr"),
     "spmv_chunks": _spmv_ids("spmv_vstream_kernel") + _spmv_ids("spmv_sweep_kernel") + _ids("spmm") + _ids("sharded_spmv"),
@@ -434,7 +435,7 @@ ALIASES = ("spmv_tinfo", "spmv_eoff")      # pointers into the allocation of spm
 
 
 # ---------------------------------------------------------------------------------------------------------
-# 5. completeness, by source scan
+# 5. completeness: what execution cannot show, by source scan (the rest is executed: tests/host_handle_check.cpp)
 # ---------------------------------------------------------------------------------------------------------
 def _source(name):
     with open(os.path.join(CSRC, name)) as f:
@@ -442,7 +443,7 @@ def _source(name):
 
 
 def function_body(text, signature):
-    """the text between the braces of the function whose definition starts with `signature`"""
+    """the text between the braces of the function (or struct) whose definition starts with `signature`"""
     at = text.index(signature)
     depth, start = 0, text.index("{", at)
     for i in range(start, len(text)):
@@ -452,81 +453,120 @@ def function_body(text, signature):
     raise AssertionError("unbalanced braces after " + signature)
 
 
-def released_fields(body, bodies):
-    """the fields of bmsp_matrix_s a function returns to the pool: pool_free(m->x), pool_free(<loop variable>.mem) for a loop over a member
-    array of views / plans, free_matrix(m->x), and what the drop_* functions it calls release"""
-    out = set(re.findall(r"pool_free\(m->(\w+)\)", body)) | set(re.findall(r"free_matrix\(m->(\w+)\)", body))
-    if re.search(r"pool_free\(\w+\.mem\)", body):
-        containers = re.findall(r"for \([^;)]*: m->(\w+)\)", body)
-        assert len(containers) == 1, containers
-        out.add(containers[0])
-    for callee in re.findall(r"\b(drop_\w+)\(m\)", body):
-        out |= released_fields(bodies[callee], bodies)
+GROUPS = ("bmsp_value_caches", "bmsp_structure_caches")
+NESTED = ("bmsp_spmv_op_view", "bmsp_spsv_plan_s")      # member arrays of the structure group; each element owns one allocation (`mem`)
+
+
+def _declarations(struct_text):
+    for line in struct_text.splitlines():
+        line = line.split("//")[0]
+        if "(" not in line:     # (methods)
+            yield line
+
+
+def raw_pointers(struct_text):
+    """the members of a struct that are plain pointers"""
+    out = set()
+    for line in _declarations(struct_text):
+        if re.match(r"\s*(?:const\s+)?[\w:]+\s*\*", line):
+            out |= set(re.findall(r"\*\s*(\w+)", line))
+    return out
+
+
+def owning_members(struct_text):
+    """the members of a struct that own memory: a DevBuf, an array of views / plans, a matrix pointer"""
+    out = set()
+    for line in _declarations(struct_text):
+        m = re.match(r"\s*bmsp::DevBuf<[\w ]+>\s+([^;]+);", line)
+        if m:
+            out |= {n.strip() for n in m.group(1).split(",")}
+        m = re.match(r"\s*(?:%s)\s+(\w+)\[" % "|".join(NESTED), line) or re.match(r"\s*bmsp::MatrixPtr\s+(\w+);", line)
+        if m:
+            out.add(m.group(1))
+    return out
+
+
+def member_names(struct_text):
+    out = set()
+    for line in _declarations(struct_text):
+        m = re.match(r"\s*(?:const\s+)?[\w:]+(?:<[\w:, ]+>)?\s*\*?\s*(\w[^;]*);", line)
+        if m:
+            out |= {re.match(r"\*?\s*(\w+)", n.strip()).group(1) for n in m.group(1).split(",")}
     return out
 
 
 @functools.lru_cache(maxsize=None)
-def scan_sources():
-    builder, spsv = _source("builder.hip"), _source("spsv.hip")
+def scan_handle():
+    """(owning members of the two groups, {struct: its text} for the groups, the handle and the nested structs, bodies of the functions
+    that drop caches)"""
+    header, builder = _source("matrix.h"), _source("builder.hip")
+    texts = {g: function_body(header, "struct %s {" % g) for g in GROUPS + NESTED}
+    texts["bmsp_matrix_s"] = function_body(header, "struct bmsp_matrix_s :")
     bodies = {"free_matrix": function_body(builder, "void free_matrix(bmsp_matrix_s *m)"),
               "invalidate_matrix": function_body(builder, "void invalidate_matrix(bmsp_matrix_s *m, int structure_changed)"),
-              "drop_spmv_op_views": function_body(builder, "void drop_spmv_op_views(bmsp_matrix_s *m)"),
-              "drop_spsv_plans": function_body(spsv, "void drop_spsv_plans(bmsp_matrix_s *m)")}
-    freed = released_fields(bodies["free_matrix"], bodies) - set(PUBLIC)
-    dropped = released_fields(bodies["invalidate_matrix"], bodies)
-    struct = function_body(_source("matrix.h"), "struct bmsp_matrix_s {")
-    pointers = set()
-    for line in struct.splitlines():
-        line = line.split("//")[0]
-        if "(" in line:
-            continue
-        m = re.match(r"\s*(?:const\s+)?[\w:]+\s*\*", line)
-        if m:
-            pointers |= set(re.findall(r"\*\s*(\w+)", line))
-    return bodies, freed, dropped, pointers
+              "drop_value_caches": function_body(builder, "void drop_value_caches(bmsp_matrix_s *m)")}
+    owning = set().union(*(owning_members(texts[g]) for g in GROUPS))
+    return owning, texts, bodies
 
 
 def test_invalidate_releases_every_pooled_field():
-    """every field free_matrix returns to the pool, other than the four public arrays, is also released by invalidate_matrix(m, 1) --
-    directly or through a drop_* it calls -- and reset, so that the next call rebuilds it instead of reading freed memory; and free_matrix
-    itself forgets no pointer member of the struct.  This fails the moment a cache is added without its line in the list"""
-    bodies, freed, dropped, pointers = scan_sources()
-    assert len(freed) >= 28, sorted(freed)
-    assert freed - dropped == set(), "bmsp_matrix_invalidate(m, 1) does not release: %s" % sorted(freed - dropped)
-    assert pointers - set(PUBLIC) - set(ALIASES) - freed == set(), "free_matrix forgets: %s" % sorted(pointers - set(PUBLIC) - set(ALIASES) - freed)
+    """Every allocation a handle caches has an owner, and the owners live in the two groups that bmsp_matrix_invalidate assigns afresh:
+    no pointer member of the handle, of a group or of a view / plan is raw but the four public arrays and the two aliases into spmv_pos,
+    the handle itself declares no owner beside the groups, and the functions that drop caches return nothing to the pool by hand.  What
+    the resets then do to a filled handle -- every release, every default, the new uid -- is executed by tests/host_handle_check.cpp
+    (test_abi.py), which must name every member of the groups.  This fails the moment a cache is added as a plain pointer"""
+    owning, texts, bodies = scan_handle()
+    assert len(owning) >= 28, sorted(owning)
+    raw = {name: raw_pointers(text) for name, text in texts.items()}
+    assert raw["bmsp_matrix_s"] == set(PUBLIC), raw["bmsp_matrix_s"]
+    assert raw["bmsp_structure_caches"] == set(ALIASES) and raw["bmsp_value_caches"] == set(), raw
+    for n in NESTED:
+        assert raw[n] == set() and owning_members(texts[n]) == {"mem"}, (n, raw[n])
+    assert owning_members(texts["bmsp_matrix_s"]) == set(), "an owner outside the groups is not reset by bmsp_matrix_invalidate"
+    assert re.search(r"struct bmsp_matrix_s : bmsp_value_caches, bmsp_structure_caches \{", _source("matrix.h"))
+    for fn, body in bodies.items():
+        assert "pool_free(" not in body and "= nullptr" not in body, fn
     inv = bodies["invalidate_matrix"]
-    assert inv.index("if (!structure_changed) return;") < inv.index("pool_free(m->rowptr)")
-    scalar = {"shard_view"}
-    for f in sorted(set(re.findall(r"pool_free\(m->(\w+)\)", inv)) | scalar | set(ALIASES)):
-        assert re.search(r"m->%s = nullptr;" % f, inv), "%s is released but not reset" % f
-    for fn in ("drop_spmv_op_views", "drop_spsv_plans"):
-        for f in re.findall(r"pool_free\(m->(\w+)\)", bodies[fn]):
-            assert re.search(r"m->%s = nullptr;" % f, bodies[fn]), (fn, f)
-    # the flags and counters that say "built" or "tried" go with what they describe
-    for reset in ("m->rowptr_rows = 0", "m->max_row_blocks = -1", "m->struct_hash = 0", "m->sp_a_hash = 0", "m->sp_b_hash = 0", "m->spmv_pos_tried = 0",
-                  "m->spmv_cw_tried = 0", "m->col_index_tried = 0", "m->sp_n_tasks = 0", "m->tp_src_uid = 0", "m->add_a_uid = 0", "m->add_b_uid = 0",
-                  "m->values_finite = -1", "m->uid = next_matrix_uid()", "m->shard_world = 0", "m->shard_bounds.clear()"):
-        assert reset in inv, reset
-    assert "m->ilu0_missing_row = -2" in bodies["drop_spmv_op_views"]
+    assert inv.index("hipDeviceSynchronize()") < inv.index("m->reset_value_caches();") < inv.index("if (structure_changed) m->reset_structure_caches();")
+    handle = texts["bmsp_matrix_s"]
+    assert "static_cast<bmsp_value_caches &>(*this) = bmsp_value_caches();" in function_body(handle, "void reset_value_caches()")
+    reset = function_body(handle, "void reset_structure_caches()")
+    assert "static_cast<bmsp_structure_caches &>(*this) = bmsp_structure_caches();" in reset and "uid = bmsp::next_matrix_uid();" in reset
+    assert "bmsp::pool_free(keys); bmsp::pool_free(bmps); bmsp::pool_free(offsets); bmsp::pool_free(values);" in function_body(handle, "void release_arrays()")
+    assert "holds_memory()" in bodies["drop_value_caches"] and "m->values_finite = -1" in bodies["drop_value_caches"]
+    for g in GROUPS:        # the value group's question: every owner of the group, and nothing else
+        if g == "bmsp_value_caches":
+            asked = set(re.findall(r"\w+", function_body(texts[g], "bool holds_memory() const")))
+            assert asked - {"return"} == owning_members(texts[g]), asked
+    with open(os.path.join(REPO, "tests", "host_handle_check.cpp")) as f:
+        check = f.read()
+    for g in GROUPS:
+        missing = {n for n in member_names(texts[g]) if not re.search(r"\b%s\b" % n, check)}
+        assert missing == set(), "tests/host_handle_check.cpp does not name: %s" % sorted(missing)
+    for name in os.listdir(CSRC):       # the sub-lists are gone, not moved
+        assert not re.search(r"\bdrop_spmv_op_views\b|\bdrop_spsv_plans\b", _source(name)), name
 
 
-@pytest.mark.parametrize("line,fn,lost", [("pool_free(m->col_mass); ", "invalidate_matrix", {"col_mass"}),
-                                          ("pool_free(m->krylov_ws); ", "drop_spmv_op_views", {"krylov_ws"}),
-                                          ("drop_spsv_plans(m);", "invalidate_matrix", {"spsv_plans", "spitsv_tmp"}),
-                                          ("free_matrix(m->shard_view); ", "invalidate_matrix", {"shard_view"})])
-def test_the_scan_notices_a_forgotten_line(line, fn, lost):
-    """the scan itself, on the text: with one release taken out of invalidate_matrix or of a drop_* it calls, exactly that field is missed"""
-    bodies, freed, _, _ = scan_sources()
-    mutated = dict(bodies)
-    assert line in mutated[fn]
-    mutated[fn] = mutated[fn].replace(line, "")
-    assert freed - released_fields(mutated["invalidate_matrix"], mutated) == lost
+@pytest.mark.parametrize("group,line,lost", [("bmsp_structure_caches", "    uint32_t *x = nullptr;", {"x"}),
+                                             ("bmsp_value_caches", "    void *x = nullptr;   // a new operand form", {"x"}),
+                                             ("bmsp_structure_caches", "    const uint64_t *x = nullptr, *y = nullptr;", {"x", "y"}),
+                                             ("bmsp_structure_caches", "    bmsp::DevBuf<uint32_t> x;", set())],
+                         ids=["structure-uint32", "value-void", "structure-two", "structure-owned"])
+def test_the_scan_notices_a_forgotten_line(group, line, lost):
+    """the scan itself, on the text: with a plain pointer member added to a group exactly that member is reported (and an owned one is not)"""
+    _, texts, _ = scan_handle()
+    before = raw_pointers(texts[group])
+    mutated = texts[group] + "\n" + line + "\n"
+    assert raw_pointers(mutated) - before == lost
+    assert member_names(mutated) - member_names(texts[group]) == (lost or {"x"})
 
 
 def test_caches_table_covers_the_scanned_set():
-    """CACHES names exactly the scanned fields, and every case id in it exists: a new cache without a case fails here"""
-    _, freed, _, _ = scan_sources()
-    assert set(CACHES) == freed, (sorted(set(CACHES) - freed), sorted(freed - set(CACHES)))
+    """CACHES names exactly the owning members of the two groups (csrc/matrix.h), and every case id in it exists: a new cache without a
+    case fails here"""
+    owning, _, _ = scan_handle()
+    assert len(owning) >= 28, sorted(owning)
+    assert set(CACHES) == owning, (sorted(set(CACHES) - owning), sorted(owning - set(CACHES)))
     ids = all_case_ids()
     import test_zzzzzzzz_structure_invalidate as gpu_cases
     for f in FAMILIES:
