@@ -856,6 +856,60 @@ int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *p
     BMSP_API_END
 }
 
+int bmsp_mg_create(int levels, const bmsp_matrix_t *A, const bmsp_matrix_t *P, const bmsp_matrix_t *R, const void *d_coarse_inv, int64_t ld_inv,
+                   double omega, int pre, int post, void *stream, bmsp_mg_t *out)
+{
+    BMSP_API_BEGIN
+    mg_check_args(levels, omega, pre, post, d_coarse_inv);
+    need(out, "out"); need(A, "A");
+    if (levels > 1) need(P, "P");
+    for (int l = 0; l < levels; l++) {
+        if (!A[l]) fail(BMSP_ERR_INVALID, "A[%d] is null", l);
+        if (l + 1 < levels && !P[l]) fail(BMSP_ERR_INVALID, "P[%d] is null", l);
+    }
+    mg_check_operands(levels, A, P, R, d_coarse_inv, ld_inv);
+    load_kernels();
+    *out = mg_create(levels, A, P, R, d_coarse_inv, ld_inv, omega, pre, post, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_mg_free(bmsp_mg_t mg)
+{
+    BMSP_API_BEGIN
+    mg_free(mg);
+    BMSP_API_END
+}
+
+int bmsp_mg_info(bmsp_mg_t mg, bmsp_mg_info_t *info)
+{
+    BMSP_API_BEGIN
+    need(mg, "mg"); need(info, "info");
+    mg_info(mg, info);
+    BMSP_API_END
+}
+
+int bmsp_mg_vcycle(bmsp_mg_t mg, const void *d_r, void *d_z, void *stream)
+{
+    BMSP_API_BEGIN
+    need(mg, "mg"); need(d_r, "d_r"); need(d_z, "d_z");
+    if (d_r == d_z) fail(BMSP_ERR_INVALID, "d_z must not be d_r: r is read after z has been written");
+    load_kernels();
+    mg_vcycle(mg, d_r, d_z, nullptr, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags, double *relres_history,
+                  bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    krylov_check_args(BMSP_OP_N, method, nullptr, max_iter, tol, flags, relres_history);
+    need(mg, "mg"); need(d_b, "d_b"); need(d_x, "d_x");
+    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    load_kernels();
+    mg_solve(mg, method, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                    uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
 {

@@ -34,6 +34,10 @@ constexpr int kChunk = 4 * kThreads;  // elements per workgroup: lane t takes ba
 // and 2048 chunks: 384 is interpolated from those points (2.7 us saved by the launch, 11 ns per ticket beyond 128 chunks).
 // BMSP_VEC_DOT_FINISH=ticket|launch forces one (read per call); the bits are the same.
 constexpr int64_t kTicketMaxChunks = 384;
+// The preconditioner kind of a hooked solve (krylov_solve_hooked: bmsp_mg_solve's cycle), internal: the public kinds end at
+// BMSP_PC_ILU_SWEEPS and bmsp_krylov_solve refuses everything beyond.  The step kernels treat it like the ILU kinds: z, ph and sh are
+// vectors of their own, written by the application, followed by kStepDotRZ in CG.
+constexpr int kPcHook = BMSP_PC_ILU_SWEEPS + 1;
 
 // The scalars of one solve, device-resident.  `stopped` is what every kernel reads first; `status` is a BMSP_KRYLOV_* value.
 struct KrylovState {
@@ -425,14 +429,14 @@ std::mutex g_dot_mu;
 std::map<std::pair<int, hipStream_t>, DotScratch> g_dot_scratch;
 
 template <typename R>
-void run_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const void *b, void *x, int64_t m, double tol, int flags,
-               double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+void run_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const KrylovHook *hook, const char *hook_name, const void *b,
+               void *x, int64_t m, double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
 {
     const int64_t n = A->num_rows;
-    const int kind = pc ? pc->kind : BMSP_PC_NONE;
+    const int kind = hook ? kPcHook : (pc ? pc->kind : BMSP_PC_NONE);
     const bool bicg = method == BMSP_KRYLOV_BICGSTAB, checked = !no_check(tol), x0 = (flags & BMSP_KRYLOV_X0_GIVEN) != 0;
-    const bool ilu = kind == BMSP_PC_ILU_EXACT || kind == BMSP_PC_ILU_SWEEPS;
-    bmsp_matrix_s *F = ilu ? pc->F : nullptr;
+    const bool ilu = kind == BMSP_PC_ILU_EXACT || kind == BMSP_PC_ILU_SWEEPS || kind == kPcHook;  // (applied through ilu_apply)
+    bmsp_matrix_s *F = ilu && !hook ? pc->F : nullptr;
     const int nvec = bicg ? 8 : 4;
     const int64_t chunks = chunks_of(n);
     // workspace: state | partials | diagonal | vectors | records
@@ -466,13 +470,15 @@ void run_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, con
     if (info) {
         memset(info, 0, sizeof *info);
         static const char *const names[4] = {"none", "jacobi", "ilu", "ilu_sweeps"};
-        snprintf(info->method, sizeof info->method, "%s+%s", bicg ? "bicgstab" : "cg", names[kind]);
+        snprintf(info->method, sizeof info->method, "%s+%s", bicg ? "bicgstab" : "cg", hook ? hook_name : names[kind]);
         info->max_iterations = m;
         info->workspace_bytes = (int64_t)A->krylov_ws_bytes;
     }
     const auto product = [&](const R *in, R *out) { spmv_op(A, op, 1.0, in, 0.0, out, st); };
-    // out = M^-1 in for the ILU kinds, through tmp: L then U; under op T the transposed factors, U^T then L^T
+    // out = M^-1 in for the ILU kinds, through tmp: L then U; under op T the transposed factors, U^T then L^T.  A hooked solve: the hook,
+    // which gets the status word every kernel of the solver reads first.
     const auto ilu_apply = [&](const R *in, R *tmp, R *out) {
+        if (hook) return (*hook)(in, out, &a.S->stopped, st);
         const int first = op == BMSP_OP_T ? BMSP_FILL_UPPER : BMSP_FILL_LOWER;
         for (int half = 0; half < 2; half++) {
             const int fill = half == 0 ? first : 1 - first;
@@ -697,8 +703,20 @@ void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, 
         }
         return;
     }
-    if (A->dtype == BMSP_F64) run_solve<double>(A, op, method, pc, b, x, m, tol, flags, relres_history, info, st);
-    else run_solve<float>(A, op, method, pc, b, x, m, tol, flags, relres_history, info, st);
+    if (A->dtype == BMSP_F64) run_solve<double>(A, op, method, pc, nullptr, nullptr, b, x, m, tol, flags, relres_history, info, st);
+    else run_solve<float>(A, op, method, pc, nullptr, nullptr, b, x, m, tol, flags, relres_history, info, st);
+}
+
+// bmsp_krylov_solve for op N with the preconditioner given as a callable (info->method: "<method>+<name>"); the arguments were checked
+// at the C boundary
+void krylov_solve_hooked(bmsp_matrix_s *A, int method, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
+                         double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+{
+    const int64_t n = A->num_rows;
+    if (n == 0) return krylov_solve(A, BMSP_OP_N, method, nullptr, b, x, max_iter, tol, flags, relres_history, info, st);
+    const int64_t m = max_iter ? max_iter : (n < kMaxIter ? n : kMaxIter);
+    if (A->dtype == BMSP_F64) run_solve<double>(A, BMSP_OP_N, method, nullptr, &hook, name, b, x, m, tol, flags, relres_history, info, st);
+    else run_solve<float>(A, BMSP_OP_N, method, nullptr, &hook, name, b, x, m, tol, flags, relres_history, info, st);
 }
 
 }  // namespace bmsp

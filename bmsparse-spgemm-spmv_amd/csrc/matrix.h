@@ -5,6 +5,7 @@
 
 #include "mac_choice.h"
 #include "runtime.h"
+#include <functional>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -400,6 +401,22 @@ void krylov_check_args(int op, int method, const bmsp_precond *pc, int64_t max_i
 void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc, const void *b, const void *x);
 void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const void *b, void *x, int64_t max_iter, double tol,
                   int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+// out = M^-1 in, enqueued on the stream; `stopped` is the solve's status word on the device, which the hook's kernels read first
+using KrylovHook = std::function<void(const void *in, void *out, const int *stopped, hipStream_t st)>;
+void krylov_solve_hooked(bmsp_matrix_s *A, int method, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
+                         double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+// multigrid.hip: the V-cycle of a caller-supplied hierarchy (the operators borrowed; diagonals, the coarse inverse and the work vectors
+// owned by the handle), enqueued on `st`, and CG / BiCGStab for A[0] x = b preconditioned by it.  mg_create synchronises `st`.
+void mg_check_args(int levels, double omega, int pre, int post, const void *d_coarse_inv);
+void mg_check_operands(int levels, bmsp_matrix_s *const *A, bmsp_matrix_s *const *P, bmsp_matrix_s *const *R, const void *d_coarse_inv,
+                       int64_t ld_inv);
+bmsp_mg_s *mg_create(int levels, bmsp_matrix_s *const *A, bmsp_matrix_s *const *P, bmsp_matrix_s *const *R, const void *d_coarse_inv,
+                     int64_t ld_inv, double omega, int pre, int post, hipStream_t st);
+void mg_free(bmsp_mg_s *mg);
+void mg_info(bmsp_mg_s *mg, bmsp_mg_info_t *info);
+void mg_vcycle(bmsp_mg_s *mg, const void *r, void *z, const int *stopped, hipStream_t st);
+void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+              bmsp_krylov_info *info, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

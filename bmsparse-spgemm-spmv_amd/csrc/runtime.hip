@@ -199,6 +199,7 @@ void warm_ilu0(hipStream_t st);
 void warm_krylov(hipStream_t st);
 void warm_reorder(hipStream_t st);
 void warm_aggregate(hipStream_t st);
+void warm_multigrid(hipStream_t st);
 
 void *host_slot_acquire();
 void host_slot_release(void *p);
@@ -242,6 +243,7 @@ void load_kernels()
     warm_krylov(nullptr);
     warm_reorder(nullptr);
     warm_aggregate(nullptr);
+    warm_multigrid(nullptr);
     // the first pinned host page and the first device-to-host copy of a process cost ~15 ms (measured inside the first product's T_1):
     // taken here too, with a copy through the slot
     // ... and so does the first timed event of a process (the stage timers' events; the queue is switched to profiling)

@@ -2,7 +2,8 @@
 // sweeps): where the tile records of (A, op) come from and how one is read, the fused multiply-add of the substitution, the cached plan
 // of (A, op, fill) -- its build and the refusal it carries -- and the walk of one block-row by eight lanes (spsv_block_row: spsv.hip
 // with one vector, spitsv.hip with the previous and the next iterate).  The kernels stay in their files: they differ in what a lane
-// owns (a row there, a column of X in spsm.hip) and in what orders them (levels there, nothing in a sweep).
+// owns (a row there, a column of X in spsm.hip) and in what orders them (levels there, nothing in a sweep).  multigrid.hip's row kernel
+// takes the record read, the fused multiply-add and the chain over one tile's row from here as well.
 #ifndef BMSP_SPSV_PLAN_HIP_H_
 #define BMSP_SPSV_PLAN_HIP_H_
 
@@ -31,6 +32,90 @@ __device__ __forceinline__ uint4 spsv_rec(const SpsvTiles &T, uint64_t t)
 
 __device__ __forceinline__ float fused(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fused(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// Row i of one tile into the chain s: s = fma(+-a_ic, x_c, s) per stored entry (i, c) of the tile, c ascending (ASCENDING) or descending,
+// one fused multiply-add each.  tx: the eight x of the tile's block column; tv: the tile's values.  The triangular solves subtract
+// (NEG); multigrid.hip's row kernel walks whole block-rows with either sign.
+template <typename S, bool MINOR, bool ASCENDING, bool NEG>
+__device__ __forceinline__ typename TileValue<S>::F tile_row_chain(uint64_t bmp, const S *tv, const typename TileValue<S>::F *tx, int i,
+                                                                   typename TileValue<S>::F s)
+{
+#pragma clang fp contract(off)
+    using D = TileValue<S>;
+    using F = typename D::F;
+    const auto term = [](S v) -> F { return NEG ? -D::load(v) : D::load(v); };
+    if (!MINOR) {
+        uint32_t byte = tile_byte(bmp, i);
+        if (ASCENDING) {
+            int k = tile_rank(bmp, 8 * i);
+            while (byte) {
+                const int c = __builtin_clz(byte) - 24;
+                byte &= ~(0x80u >> c);
+                s = fused(term(tv[k++]), tx[c], s);
+            }
+        } else {
+            int k = tile_rank(bmp, 8 * i) + __builtin_popcount(byte);
+            while (byte) {
+                const int c = 7 - __builtin_ctz(byte);
+                byte &= byte - 1;
+                s = fused(term(tv[--k]), tx[c], s);
+            }
+        }
+    } else {
+        uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
+        while (m) {
+            int p;
+            if (ASCENDING) p = tile_pop_first(m);
+            else { p = 63 - __builtin_ctzll(m); m &= m - 1; }
+            s = fused(term(tv[tile_rank(bmp, p)]), tx[p >> 3], s);
+        }
+    }
+    return s;
+}
+
+// The same chain in two halves, for walks that keep several tiles in flight (multigrid.hip): tile_row_gather loads row i's stored values
+// of one tile and the x they meet into registers, in column order, and returns their number; tile_row_fold takes them into the chain.
+// Between the two the loads of further tiles can be issued: the chain itself is tile_row_chain's, term by term.
+template <typename S, bool MINOR>
+__device__ __forceinline__ int tile_row_gather(uint64_t bmp, const S *tv, const typename TileValue<S>::F *tx, int i,
+                                               typename TileValue<S>::F (&a)[8], typename TileValue<S>::F (&x)[8])
+{
+    using D = TileValue<S>;
+    int cnt = 0;
+    if (!MINOR) {
+        uint32_t byte = tile_byte(bmp, i);
+        const int k0 = tile_rank(bmp, 8 * i);
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+            if (byte) {
+                const int c = __builtin_clz(byte) - 24;
+                byte &= ~(0x80u >> c);
+                a[q] = D::load(tv[k0 + q]);
+                x[q] = tx[c];
+                cnt = q + 1;
+            }
+    } else {
+        uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+            if (m) {
+                const int p = tile_pop_first(m);
+                a[q] = D::load(tv[tile_rank(bmp, p)]);
+                x[q] = tx[p >> 3];
+                cnt = q + 1;
+            }
+    }
+    return cnt;
+}
+template <typename F, bool NEG>
+__device__ __forceinline__ F tile_row_fold(const F (&a)[8], const F (&x)[8], int cnt, F s)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int q = 0; q < 8; q++)
+        if (q < cnt) s = fused(NEG ? -a[q] : a[q], x[q], s);
+    return s;
+}
 
 // Lane i of a group of eight computes row i of output block I and returns it (stored too when the row exists).  The x of the tiles off
 // the block diagonal is read from x_in, the row is written to x_out, inside the diagonal tile the group's new values go round by shuffle.
@@ -66,32 +151,7 @@ __device__ __forceinline__ typename TileValue<S>::F spsv_block_row(const SpsvTil
         const uint64_t bmp = (uint64_t)r.y << 32 | r.x;
         const S *tv = vals + r.z;
         const F *tx = x_in + (uint64_t)r.w * 8;  // only stored entries index it: never beyond the matrix
-        if (!MINOR) {
-            uint32_t byte = tile_byte(bmp, i);
-            if (LOWER) {
-                int k = tile_rank(bmp, 8 * i);
-                while (byte) {
-                    const int c = __builtin_clz(byte) - 24;
-                    byte &= ~(0x80u >> c);
-                    s = fused(-D::load(tv[k++]), tx[c], s);
-                }
-            } else {
-                int k = tile_rank(bmp, 8 * i) + __builtin_popcount(byte);
-                while (byte) {
-                    const int c = 7 - __builtin_ctz(byte);
-                    byte &= byte - 1;
-                    s = fused(-D::load(tv[--k]), tx[c], s);
-                }
-            }
-        } else {
-            uint64_t m = bmp & (0x8080808080808080ull >> i);  // positions 8j + i
-            while (m) {
-                int p;
-                if (LOWER) p = tile_pop_first(m);
-                else { p = 63 - __builtin_ctzll(m); m &= m - 1; }
-                s = fused(-D::load(tv[tile_rank(bmp, p)]), tx[p >> 3], s);
-            }
-        }
+        s = tile_row_chain<S, MINOR, LOWER, true>(bmp, tv, tx, i, s);
     }
     F xi = s;  // no diagonal tile (unit diagonal): nothing inside the block
     if (diag) {

@@ -36,6 +36,8 @@ PC_NONE, PC_JACOBI, PC_ILU_EXACT, PC_ILU_SWEEPS = 0, 1, 2, 3
 KRYLOV_X0_GIVEN = 1
 KRYLOV_NO_CHECK = -1.0
 KRYLOV_MAXITER, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN = 0, 1, 2
+MG_MAX_LEVELS = 16
+MG_RESTRICT_ROW, MG_RESTRICT_SPMV, MG_RESTRICT_PT = 0, 1, 2
 _METHODS = {"cg": KRYLOV_CG, "bicgstab": KRYLOV_BICGSTAB, KRYLOV_CG: KRYLOV_CG, KRYLOV_BICGSTAB: KRYLOV_BICGSTAB}
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
@@ -51,7 +53,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -191,6 +193,18 @@ class KrylovInfo(C.Structure):
         return d
 
 
+class MgInfo(C.Structure):
+    _fields_ = [("levels", C.c_int), ("pre", C.c_int), ("post", C.c_int), ("coarse_exact", C.c_int), ("n", C.c_int64 * MG_MAX_LEVELS),
+                ("restrict_mode", C.c_int * MG_MAX_LEVELS), ("kernel", C.c_char * 64), ("coarse_kernel", C.c_char * 64),
+                ("workspace_bytes", C.c_int64), ("launches_per_cycle", C.c_int64)]
+
+    def as_dict(self):
+        return {"levels": self.levels, "pre": self.pre, "post": self.post, "coarse_exact": self.coarse_exact,
+                "n": list(self.n)[:self.levels], "restrict_mode": list(self.restrict_mode)[:max(self.levels - 1, 0)],
+                "kernel": self.kernel.decode(), "coarse_kernel": self.coarse_kernel.decode(), "workspace_bytes": self.workspace_bytes,
+                "launches_per_cycle": self.launches_per_cycle}
+
+
 class ShardStats(C.Structure):
     _fields_ = [("world", C.c_int), ("rank", C.c_int), ("panel_block_row_begin", C.c_int64), ("panel_block_row_end", C.c_int64),
                 ("panel_tasks", C.c_int64), ("exchange_bytes", C.c_int64), ("exchange_us", C.c_double), ("exchange_exposed_us", C.c_double),
@@ -279,6 +293,11 @@ def lib():
         L.bmsp_matrix_aggregate.argtypes = [vp, C.c_uint64, vp, p(i64), vp, p(AggregateInfo)]
         L.bmsp_matrix_from_aggregates.argtypes = [i, i, vp, vp, i, i, vp, p(vp)]
         L.bmsp_krylov_solve.argtypes =[vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_mg_create.argtypes = [i, vp, vp, vp, vp, i64, C.c_double, i, i, vp, p(vp)]
+        L.bmsp_mg_free.argtypes = [vp]
+        L.bmsp_mg_info.argtypes = [vp, p(MgInfo)]
+        L.bmsp_mg_vcycle.argtypes = [vp, vp, vp, vp]
+        L.bmsp_mg_solve.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -1145,6 +1164,82 @@ def krylov_solve(A, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, 
     del keep
     d = info.as_dict()
     return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+
+
+class Multigrid:
+    """The V-cycle of a hierarchy on the device (bmsp_mg_create): A a list of `levels` square BmSpMatrix (F32 or F64, one dtype), P a list
+    of levels - 1 prolongators (n_l x n_{l+1}), R None (restrict by P^T) or a list of restrictions / None entries, coarse_inv None or the
+    dense inverse of A[-1] (numpy array or DeviceArray, row-major; ld_inv its leading dimension when it is not n_c), omega the damping
+    of the Jacobi steps, pre / post their numbers.  Any operator in either tile layout.  The object keeps the operators alive; the
+    library copies the diagonals and the inverse at construction, so new values of A mean a new Multigrid.  CG needs a symmetric
+    cycle: R = P^T and pre == post."""
+
+    def __init__(self, A, P, R=None, coarse_inv=None, omega=2.0 / 3.0, pre=1, post=1, ld_inv=None, stream=None):
+        A, P = list(A), list(P)
+        R = None if R is None else list(R)
+        levels = len(A)
+        if len(P) != max(levels - 1, 0) or (R is not None and len(R) != len(P)):
+            raise ValueError("P (and R) must hold len(A) - 1 operators")
+        self._keep = (A, P, R)
+        self.h = None
+        vt = np.dtype(OUT_DTYPE[A[0].info()["dtype"]]) if levels else np.dtype(np.float32)
+        self.dtype, self.n = vt, (A[0].info()["num_rows"] if levels else 0)
+        handles = lambda ms: (C.c_void_p * max(len(ms), 1))(*[None if m is None else m.h for m in ms])
+        inv = coarse_inv
+        if inv is not None and not isinstance(inv, DeviceArray):
+            a = np.ascontiguousarray(inv, vt)
+            if ld_inv is None:
+                ld_inv = a.shape[1] if a.ndim == 2 else A[-1].info()["num_rows"]
+            inv = DeviceArray.from_host(a.ravel())
+        if ld_inv is None:
+            ld_inv = A[-1].info()["num_rows"] if levels else 0
+        h = C.c_void_p()
+        check(lib().bmsp_mg_create(levels, handles(A), handles(P), None if R is None else handles(R), None if inv is None else inv.ptr,
+                                   int(ld_inv), float(omega), int(pre), int(post), stream, C.byref(h)))
+        self.h = h.value
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.bmsp_mg_free(self.h)
+            self.h = None
+
+    def info(self):
+        i = MgInfo()
+        check(lib().bmsp_mg_info(self.h, C.byref(i)))
+        return i.as_dict()
+
+    def vcycle(self, r, z=None, stream=None):
+        """z = one cycle for right-hand side r from z = 0 (DeviceArrays of the vector type; z is made when None), asynchronous on `stream`"""
+        if r.dtype != self.dtype or r.n < self.n:
+            raise ValueError("r must hold %d entries of %s" % (self.n, self.dtype.name))
+        if z is None:
+            z = DeviceArray(self.n, self.dtype)
+        elif z.dtype != self.dtype or z.n < self.n:
+            raise ValueError("z must hold %d entries of %s" % (self.n, self.dtype.name))
+        check(lib().bmsp_mg_vcycle(self.h, r.ptr, z.ptr, stream))
+        return z
+
+    def solve(self, b, method="cg", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+        """A[0] * x = b by CG or BiCGStab preconditioned by one cycle (bmsp_mg_solve): krylov_solve's arguments and results"""
+        if method not in _METHODS:
+            raise ValueError("method must be 'cg' or 'bicgstab' (got %r)" % (method,))
+        if b.dtype != self.dtype or b.n < self.n:
+            raise ValueError("b must hold %d entries of %s" % (self.n, self.dtype.name))
+        if x is None:
+            if x0_given:
+                raise ValueError("x0_given needs x")
+            x = DeviceArray(self.n, self.dtype)
+        elif x.dtype != self.dtype or x.n < self.n:
+            raise ValueError("x must hold %d entries of %s" % (self.n, self.dtype.name))
+        info = KrylovInfo()
+        hist = None
+        if history:
+            cap = int(max_iter) if max_iter else min(self.n, 1 << 20)
+            hist = np.zeros(max(cap, 1), np.float64)
+        check(lib().bmsp_mg_solve(self.h, _METHODS[method], b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
+                                  hist.ctypes.data if history else None, C.byref(info), stream))
+        d = info.as_dict()
+        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
 
 
 def _spsm_strides(k, ldb, ldx):

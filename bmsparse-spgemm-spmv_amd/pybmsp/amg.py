@@ -11,7 +11,8 @@ the cycle symmetric too, but leaves the smooth error components of the coarsest 
 then grows with the grid, which the hierarchy exists to prevent.  The small host steps of the set-up are that inverse and the square
 roots of the aggregate sizes (and of the diagonal when theta != 0).
 
-Putting the cycle into bmsp_krylov_solve is not done here: this module says what such a preconditioner buys (tools/amg_bench.py)."""
+The cycle and the solve driven from Python here (vcycle, pcg) are the yardstick; device_cycle hands the same hierarchy to the library's
+enqueued cycle (pybmsp.Multigrid: bmsp_mg_vcycle, bmsp_mg_solve), and tools/amg_bench.py times the two against each other."""
 import numpy as np
 
 import pybmsp as B
@@ -71,14 +72,14 @@ def galerkin(A, P):
 
 class Level:
     """A, diag(A)^-1 as a diagonal matrix and, except on the coarsest level, P and R = P^T (row-major tiles) to the next one; on the
-    coarsest level the dense inverse of A"""
+    coarsest level the dense inverse of A (inv: a bmSparse matrix, what vcycle applies; inv_dense: the same float64 array)"""
 
     def __init__(self, A):
         i = A.info()
         self.A, self.n = A, i["num_rows"]
         ones = B.DeviceArray.from_host(np.ones(self.n, _vt(A)))
         self.Dinv = B.scale(B.from_diagonal(ones, dtype=i["dtype"]), B.diagonal(A), None, div_left=True)
-        self.P = self.R = self.inv = self.info = None
+        self.P = self.R = self.inv = self.inv_dense = self.info = None
 
 
 def build_hierarchy(A, theta=0.0, omega=2.0 / 3.0, coarse=40, max_levels=10, seed=0):
@@ -101,8 +102,16 @@ def build_hierarchy(A, theta=0.0, omega=2.0 / 3.0, coarse=40, max_levels=10, see
     dense = np.zeros((last.n, last.n))
     dense[r, c] = v
     rr, cc = [a.ravel() for a in np.meshgrid(np.arange(last.n), np.arange(last.n), indexing="ij")]
-    last.inv = B.BmSpMatrix.from_coo(last.n, last.n, rr, cc, np.linalg.inv(dense).ravel(), dtype=A.info()["dtype"])
+    last.inv_dense = np.linalg.inv(dense)
+    last.inv = B.BmSpMatrix.from_coo(last.n, last.n, rr, cc, last.inv_dense.ravel(), dtype=A.info()["dtype"])
     return levels
+
+
+def device_cycle(levels, omega=2.0 / 3.0, pre=1, post=1):
+    """the hierarchy of build_hierarchy as a pybmsp.Multigrid: the same operators (borrowed, kept alive by the object), R = P^T as built,
+    the dense inverse of the coarsest level rounded to the vector type"""
+    return B.Multigrid([lv.A for lv in levels], [lv.P for lv in levels[:-1]], [lv.R for lv in levels[:-1]], levels[-1].inv_dense, omega,
+                       pre, post)
 
 
 def _residual(lv, b, x):

@@ -402,6 +402,47 @@ inline double bmSparse_vec_dot(int64_t n, const R *x, const R *y)
     return out.to_host()[0];
 }
 
+/* Multigrid on the device (bmsp_mg_create / bmsp_mg_vcycle / bmsp_mg_solve): the V-cycle of a hierarchy of float or double matrices, and CG
+ * / BiCGStab for A[0] * x = b preconditioned by one cycle.  A holds the level operators, P the prolongators (one fewer), R the restrictions
+ * (empty, or null entries: restrict by P^T), coarse_inv (may be null) the dense inverse of the coarsest operator on the device, n_c x n_c
+ * row-major at leading dimension ld_inv (0: n_c), of the vector type.  The matrices are borrowed: they must outlive the object.  vcycle: z =
+ * one cycle for r from z = 0 (device pointers, z != r); solve: bmSparse_solve's arguments; both synchronous like bmSparse_SpMV. */
+template <class valueType> class bmSpMultigrid {
+    bmsp_mg_t h_ = nullptr;
+
+public:
+    typedef typename bmsp::vector_of<valueType>::type vectorType;
+    bmSpMultigrid(const std::vector<bmSpMatrix<valueType> *> &A, const std::vector<bmSpMatrix<valueType> *> &P,
+                  const std::vector<bmSpMatrix<valueType> *> &R = std::vector<bmSpMatrix<valueType> *>(), const vectorType *coarse_inv = nullptr,
+                  int64_t ld_inv = 0, double omega = 2.0 / 3.0, int pre = 1, int post = 1)
+    {
+        std::vector<bmsp_matrix_t> a, p, r;
+        for (size_t l = 0; l < A.size(); l++) a.push_back(A[l] ? A[l]->handle() : nullptr);
+        for (size_t l = 0; l < P.size(); l++) p.push_back(P[l] ? P[l]->handle() : nullptr);
+        for (size_t l = 0; l < R.size(); l++) r.push_back(R[l] ? R[l]->handle() : nullptr);
+        if (P.size() + 1 != A.size() || (!R.empty() && R.size() != P.size())) throw std::runtime_error("bmSpMultigrid: P (and R) hold one operator fewer than A");
+        if (ld_inv == 0 && !A.empty() && A.back()) ld_inv = A.back()->num_rows;
+        bmsp::check(bmsp_mg_create((int)a.size(), a.data(), p.empty() ? nullptr : p.data(), r.empty() ? nullptr : r.data(), coarse_inv, ld_inv,
+                                   omega, pre, post, nullptr, &h_));
+    }
+    bmSpMultigrid(const bmSpMultigrid &) = delete;
+    bmSpMultigrid &operator=(const bmSpMultigrid &) = delete;
+    ~bmSpMultigrid() { if (h_) bmsp_mg_free(h_); }
+    bmsp_mg_t handle() const { return h_; }
+    void info(bmsp_mg_info_t *out) const { bmsp::check(bmsp_mg_info(h_, out)); }
+    void vcycle(const vectorType *r, vectorType *z)
+    {
+        bmsp::check(bmsp_mg_vcycle(h_, r, z, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+    void solve(int method, const vectorType *b, vectorType *x, int64_t max_iter = 0, double tol = 1e-6, int flags = 0,
+               double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
+    {
+        bmsp::check(bmsp_mg_solve(h_, method, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+};
+
 /* Block multi-colour ordering and block permutation (bmsp_matrix_color_blocks / bmsp_matrix_permute_blocks / bmsp_vec_permute_blocks).
  * bmSparse_color_blocks: the greedy colouring of the block-row graph of a square A by hashed priorities into colors and the ordering by
  * colour class into perm (new -> old), both resized to ceil(num_rows / 8); the triangles of bmSparse_permute_blocks(A, perm, perm, B)

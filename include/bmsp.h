@@ -829,6 +829,80 @@ int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *p
                       int64_t max_iter, double tol, int flags, double *relres_history /* host, may be NULL */,
                       bmsp_krylov_info *info /* may be NULL */, void *stream);
 
+/* Multigrid on the device: the V-cycle of a hierarchy the caller supplies (pybmsp/amg.py's smoothed aggregation, a geometric one, any),
+ * enqueued on a stream like the rest of bmsp_krylov_solve, and CG / BiCGStab for A[0] * x = b preconditioned by one cycle.  The cycle is
+ * not a `kind` of bmsp_krylov_solve (bmsp_precond is fixed): it has its own handle and its own solve.  Nothing in the reference is
+ * replaced (it has no solver).
+ *   Operands: A[l] is square, n_l x n_l, F32 or F64, all of one dtype (F16: BMSP_ERR_UNSUPPORTED, as in bmsp_krylov_solve); P[l] is n_l x
+ *       n_{l+1}; R[l] is n_{l+1} x n_l, and R == NULL or R[l] == NULL restricts by P[l]^T.  Every operator may be in either tile layout,
+ *       independently of the others: tiles are in (block-row, block-column) order in both, so no view and no conversion is made.
+ *       d_coarse_inv (may be NULL) is the dense inverse of A[levels - 1], n_c x n_c row-major with leading dimension ld_inv >= n_c, of
+ *       the vector type R (float for F32, double for F64), n_c <= 4096.
+ *   The handle borrows the matrices (the caller keeps them alive; their values are read at every cycle) and owns a copy of every level's
+ *       diagonal, taken with bmsp_matrix_diagonal at create (a value update of A means a new handle), a copy of the coarse inverse stored
+ *       column by column (one lane per row: the lanes' loads coalesce) and the per-level work vectors.  bmsp_mg_create synchronises
+ *       `stream`; d_coarse_inv may go when it returns.
+ *   Arithmetic, fixed operation by operation (tests/multigrid_ref.c restates it).  Nothing is contracted except the named fma.  wR is
+ *       omega rounded once to R; d_i is the stored diagonal entry of the level's A, or +0 if none is stored.
+ *       rowchain(M, init, +-, v)_i: s = init_i, then for the stored entries (i, j) of row i in ascending j s = fma(+-m_ij, v_j, s) -- one
+ *           fused multiply-add per stored entry in column order, the convention of bmsp_spsv.
+ *       residual:     t = rowchain(A, r, -, x).
+ *       Jacobi step:  x'_i = fl(x_i + fl(wR * fl(s_i / d_i))) with s the residual chain, out of place (two buffers).  The first step from
+ *           x = 0 is x_i = fl(wR * fl(r_i / d_i)), an element-wise launch with no walk.  With pre == 0, x = 0 and t = r.
+ *       restriction:  rc = rowchain(R, +0, +, t) in row mode; bmsp_spmv_op(R, N, 1, t, 0, rc) in spmv mode; bmsp_spmv_op(P, T, 1, t, 0, rc)
+ *           where R is NULL.
+ *       prolongation: x_i = rowchain(P, x, +, e): the add is the start of the chain.
+ *       coarsest level with the inverse: s = +0, then for j = 0 .. n_c - 1 s = fma(inv_ij, r_j, s).  Without it: pre + post Jacobi steps
+ *           from zero.
+ *       recursion:    level l runs `pre` steps, the residual, the restriction, the cycle of level l + 1 for rc, the prolongation of its
+ *           result e, `post` steps.  Rows at or beyond n_l are never read or written.
+ *       How a block-row is walked is the library's choice per operator, a function of its structure alone (eight lanes per block-row
+ *       with one or four tiles in flight, or a wave per block-row whose eight lane groups gather eight tiles and pass the running sum
+ *       from group to group in tile order; BMSP_MG_WALK=group1|group4|wave forces one, read per call): the chain of a row is the same in
+ *       all of them, term by term, and so are the bits.
+ *       In row mode the cycle is therefore a pure function of its inputs: it does not depend on the grid, on scheduling or on the
+ *       stream, and uses no atomic, no flag, no spin and no LDS.  A zero or unstored diagonal is not refused: IEEE gives Inf or NaN
+ *       (BMSP_PC_JACOBI's rule) and a solve ends in BMSP_KRYLOV_BREAKDOWN.
+ *   Restriction mode per level: BMSP_MG_RESTRICT=row|spmv (read per call) forces one; the default is a function of R[l]'s structure
+ *       alone -- row mode up to 24 tiles per block-row of R[l] in the mean, spmv mode beyond (bmsp_spmv_op splits long block-rows and
+ *       sums in another order; the two were measured to cross there) -- and bmsp_mg_info reports it.  row gives the fixed bits above, spmv gives bmsp_spmv_op's.
+ *       Prolongation always takes the row kernel.
+ *   bmsp_mg_vcycle: z = one cycle for right-hand side r from z = 0 (d_z must not be d_r), asynchronous on `stream`, nothing read back.
+ *       One stream per handle at a time.  A first call that has to build a view for bmsp_spmv_op synchronises, as everywhere else.
+ *       n_0 == 0 is legal: the cycle does nothing.  bmsp_mg_free does not synchronise (bmsp_matrix_free does not either): the caller lets
+ *       what it enqueued on the handle finish first.
+ *   bmsp_mg_solve: bmsp_krylov_solve(A[0], BMSP_OP_N, method, ...) with z = M^-1 r one cycle -- its arithmetic, stop rule, breakdown
+ *       rules, BMSP_KRYLOV_CHECK ramp, BMSP_KRYLOV_NO_CHECK mode, BMSP_KRYLOV_X0_GIVEN, history, info and refusals; in CG the cycle is
+ *       followed by rho' = dot(r, z), in BiCGStab it stands where the ILU kinds stand.  info->method is "cg+mg" or "bicgstab+mg",
+ *       precond_applies counts cycles.  The workspace lives on A[0]'s handle.  The kernels of the cycle read the solver's status word
+ *       first and return without writing once the solve has stopped; only the bmsp_spmv_op calls of an iteration enqueued behind a stop
+ *       still run (the iterate of a level without a pre-smoothing step is zeroed by such a kernel too, not by a memset).  The views
+ *       bmsp_spmv_op needs for the restriction -- (P, T), or (R, N) of a column-major R in spmv mode -- are built before the first
+ *       iteration is enqueued.  CG needs a symmetric cycle: R = P^T (R NULL, or the transposes given) and pre == post; BiCGStab takes any.  n_0 == 0
+ *       returns BMSP_KRYLOV_CONVERGED after 0 iterations.
+ *   bmsp_mg_info: the levels, n per level, the restriction mode per level (BMSP_MG_RESTRICT_*; -1 on the coarsest), the kernel names,
+ *       the bytes the handle owns and the launches of one cycle (a bmsp_spmv_op call counts as one).
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing done on the device: levels outside
+ *   1 .. 16; omega not finite; pre or post outside 0 .. 16; pre + post == 0 on a level that has no exact solve; a null out, A, P (levels >
+ *   1) or entry of them; shapes that do not chain; mixed dtypes; row-panel views; n_c > 4096 with an inverse; ld_inv < n_c; for the
+ *   cycle a null handle or vector, d_z == d_r; for the solve what bmsp_krylov_solve refuses. */
+#define BMSP_MG_MAX_LEVELS 16
+#define BMSP_MG_RESTRICT_ROW 0
+#define BMSP_MG_RESTRICT_SPMV 1
+#define BMSP_MG_RESTRICT_PT 2   /* R[l] is NULL: bmsp_spmv_op(P[l], T) */
+typedef struct bmsp_mg_s *bmsp_mg_t;
+typedef struct { int levels, pre, post, coarse_exact; int64_t n[BMSP_MG_MAX_LEVELS]; int restrict_mode[BMSP_MG_MAX_LEVELS];
+                 char kernel[64], coarse_kernel[64]; int64_t workspace_bytes, launches_per_cycle; } bmsp_mg_info_t;
+int bmsp_mg_create(int levels, const bmsp_matrix_t *A /* levels */, const bmsp_matrix_t *P /* levels-1 */,
+                   const bmsp_matrix_t *R /* levels-1; NULL or NULL entries: restrict by P^T */,
+                   const void *d_coarse_inv /* n_c x n_c row-major, vector type; may be NULL */, int64_t ld_inv,
+                   double omega, int pre, int post, void *stream, bmsp_mg_t *out);
+int bmsp_mg_free(bmsp_mg_t mg);
+int bmsp_mg_info(bmsp_mg_t mg, bmsp_mg_info_t *info);
+int bmsp_mg_vcycle(bmsp_mg_t mg, const void *d_r, void *d_z, void *stream);
+int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                  double *relres_history, bmsp_krylov_info *info, void *stream);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the
