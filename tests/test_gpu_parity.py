@@ -406,6 +406,9 @@ def check_spgemm(oracle, bmsp, A_coo, B_coo, dtype, mode, tc, exact_expected=Fal
     np.testing.assert_array_equal(k, refC.keys)
     np.testing.assert_array_equal(b, refC.bmps)
     np.testing.assert_array_equal(o, refC.offsets)
+    # the block-row pointer, which four symbolic routes write by hand and the others leave to ensure_rowptr
+    want_ptr = np.searchsorted((refC.keys >> np.uint64(32)).astype(np.int64), np.arange((ar + 7) // 8 + 1), side="left")
+    np.testing.assert_array_equal(Cm.block_row_ptr(), want_ptr.astype(np.uint32))
     ref_vals = refC.values
     if exact_expected or (not mfma):
         # same operation order as the oracle (tasks k-ascending, k = 0..7 inside a task): bit-exact
