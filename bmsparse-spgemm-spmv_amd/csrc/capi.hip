@@ -856,6 +856,18 @@ int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *p
     BMSP_API_END
 }
 
+int bmsp_gmres_solve(bmsp_matrix_t A, int op, const bmsp_precond *pc, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol,
+                     int flags, double *relres_history, bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    gmres_check_args(op, restart, pc, max_iter, tol, flags, relres_history);
+    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
+    krylov_check_operands(A, pc, d_b, d_x);
+    load_kernels();
+    gmres_solve(A, op, pc, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_mg_create(int levels, const bmsp_matrix_t *A, const bmsp_matrix_t *P, const bmsp_matrix_t *R, const void *d_coarse_inv, int64_t ld_inv,
                    double omega, int pre, int post, void *stream, bmsp_mg_t *out)
 {
@@ -907,6 +919,18 @@ int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t 
     if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
     load_kernels();
     mg_solve(mg, method, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_mg_solve_gmres(bmsp_mg_t mg, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                        double *relres_history, bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    gmres_check_args(BMSP_OP_N, restart, nullptr, max_iter, tol, flags, relres_history);
+    need(mg, "mg"); need(d_b, "d_b"); need(d_x, "d_x");
+    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    load_kernels();
+    mg_solve_gmres(mg, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 

@@ -405,6 +405,13 @@ void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, 
 using KrylovHook = std::function<void(const void *in, void *out, const int *stopped, hipStream_t st)>;
 void krylov_solve_hooked(bmsp_matrix_s *A, int method, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
                          double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+// gmres.hip: restarted GMRES for op(A) x = b, enqueued on `st` like the two solvers above; restart 0 means 30.  The hooked form is
+// bmsp_mg_solve_gmres's (op N, the preconditioner a callable).
+void gmres_check_args(int op, int restart, const bmsp_precond *pc, int64_t max_iter, double tol, int flags, const double *relres_history);
+void gmres_solve(bmsp_matrix_s *A, int op, const bmsp_precond *pc, int restart, const void *b, void *x, int64_t max_iter, double tol,
+                 int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+void gmres_solve_hooked(bmsp_matrix_s *A, int restart, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
+                        double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
 // multigrid.hip: the V-cycle of a caller-supplied hierarchy (the operators borrowed; diagonals, the coarse inverse and the work vectors
 // owned by the handle), enqueued on `st`, and CG / BiCGStab for A[0] x = b preconditioned by it.  mg_create synchronises `st`.
 void mg_check_args(int levels, double omega, int pre, int post, const void *d_coarse_inv);
@@ -417,6 +424,8 @@ void mg_info(bmsp_mg_s *mg, bmsp_mg_info_t *info);
 void mg_vcycle(bmsp_mg_s *mg, const void *r, void *z, const int *stopped, hipStream_t st);
 void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
               bmsp_krylov_info *info, hipStream_t st);
+void mg_solve_gmres(bmsp_mg_s *mg, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+                    bmsp_krylov_info *info, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

@@ -479,18 +479,31 @@ void mg_info(bmsp_mg_s *mg, bmsp_mg_info_t *info)
     info->launches_per_cycle = c.launches;
 }
 
-void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-              bmsp_krylov_info *info, hipStream_t st)
+// a first call that restricts by a view of bmsp_spmv_op -- (P, T), or (R, N) of a column-major R -- builds it before the iteration is
+// enqueued, not in the middle of it (a row-major R under op N is bmsp_spmv's, whose own first call builds its plan)
+static void ensure_restriction_views(bmsp_mg_s *mg, hipStream_t st)
 {
-    // a first call that restricts by a view of bmsp_spmv_op -- (P, T), or (R, N) of a column-major R -- builds it here, not in the middle
-    // of the enqueued iteration (a row-major R under op N is bmsp_spmv's, whose own first call builds its plan)
     for (int l = 0; l + 1 < mg->levels && mg->n[0]; l++) {
         const int mode = restrict_mode(mg, l);
         if (mode == BMSP_MG_RESTRICT_PT) spmv_op_ensure_view(mg->P[(size_t)l], BMSP_OP_T, st);
         else if (mode == BMSP_MG_RESTRICT_SPMV && mg->R[(size_t)l]->transposed) spmv_op_ensure_view(mg->R[(size_t)l], BMSP_OP_N, st);
     }
+}
+
+void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+              bmsp_krylov_info *info, hipStream_t st)
+{
+    ensure_restriction_views(mg, st);
     const KrylovHook hook = [mg](const void *in, void *out, const int *stopped, hipStream_t s) { mg_vcycle(mg, in, out, stopped, s); };
     krylov_solve_hooked(mg->A[0], method, hook, "mg", b, x, max_iter, tol, flags, relres_history, info, st);
+}
+
+void mg_solve_gmres(bmsp_mg_s *mg, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+                    bmsp_krylov_info *info, hipStream_t st)
+{
+    ensure_restriction_views(mg, st);
+    const KrylovHook hook = [mg](const void *in, void *out, const int *stopped, hipStream_t s) { mg_vcycle(mg, in, out, stopped, s); };
+    gmres_solve_hooked(mg->A[0], restart, hook, "mg", b, x, max_iter, tol, flags, relres_history, info, st);
 }
 
 }  // namespace bmsp

@@ -197,6 +197,7 @@ void warm_spsm(hipStream_t st);
 void warm_spitsv(hipStream_t st);
 void warm_ilu0(hipStream_t st);
 void warm_krylov(hipStream_t st);
+void warm_gmres(hipStream_t st);
 void warm_reorder(hipStream_t st);
 void warm_aggregate(hipStream_t st);
 void warm_multigrid(hipStream_t st);
@@ -241,6 +242,7 @@ void load_kernels()
     warm_spitsv(nullptr);
     warm_ilu0(nullptr);
     warm_krylov(nullptr);
+    warm_gmres(nullptr);
     warm_reorder(nullptr);
     warm_aggregate(nullptr);
     warm_multigrid(nullptr);

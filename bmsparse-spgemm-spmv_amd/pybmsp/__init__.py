@@ -53,7 +53,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_gmres_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_mg_solve_gmres", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -293,11 +293,13 @@ def lib():
         L.bmsp_matrix_aggregate.argtypes = [vp, C.c_uint64, vp, p(i64), vp, p(AggregateInfo)]
         L.bmsp_matrix_from_aggregates.argtypes = [i, i, vp, vp, i, i, vp, p(vp)]
         L.bmsp_krylov_solve.argtypes =[vp, i, i, p(Precond), vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_gmres_solve.argtypes = [vp, i, p(Precond), i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_mg_create.argtypes = [i, vp, vp, vp, vp, i64, C.c_double, i, i, vp, p(vp)]
         L.bmsp_mg_free.argtypes = [vp]
         L.bmsp_mg_info.argtypes = [vp, p(MgInfo)]
         L.bmsp_mg_vcycle.argtypes = [vp, vp, vp, vp]
         L.bmsp_mg_solve.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_mg_solve_gmres.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -623,8 +625,16 @@ class BmSpMatrix:
         return ilu0(self, max_iter, tol, out_transposed, history, stream)
 
     def solve(self, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
-        """(x, info[, history]) with op(this) * x = b by CG or BiCGStab on the device: pybmsp.krylov_solve"""
+        """(x, info[, history]) with op(this) * x = b by CG or BiCGStab on the device: pybmsp.krylov_solve.  method "gmres" or
+        "gmres(<m>)": restarted GMRES with restart 30 or m, pybmsp.gmres_solve (solve_gmres takes the restart as a keyword)"""
+        restart = _gmres_restart(method)
+        if restart is not None:
+            return gmres_solve(self, b, precond, op, restart, max_iter, tol, x, x0_given, history, stream)
         return krylov_solve(self, b, method, precond, op, max_iter, tol, x, x0_given, history, stream)
+
+    def solve_gmres(self, b, precond=None, op="N", restart=30, max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+        """(x, info[, history]) with op(this) * x = b by restarted GMRES on the device: pybmsp.gmres_solve"""
+        return gmres_solve(self, b, precond, op, restart, max_iter, tol, x, x0_given, history, stream)
 
     def color_blocks(self, seed=0, stream=None):
         """(colors, perm, info): the greedy block colouring by hashed priorities and its ordering: pybmsp.color_blocks"""
@@ -1166,6 +1176,49 @@ def krylov_solve(A, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, 
     return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
 
 
+def _gmres_restart(method):
+    """"gmres" -> 30, "gmres(<m>)" -> m, anything else -> None"""
+    if method == "gmres":
+        return 30
+    if isinstance(method, str) and method.startswith("gmres(") and method.endswith(")") and method[6:-1].isdigit():
+        return int(method[6:-1])
+    return None
+
+
+def _solve_vectors(n, vt, b, x, x0_given, max_iter, history):
+    """the checks of a solve's vectors; returns (x, the history buffer or None)"""
+    if b.dtype != vt or b.n < n:
+        raise ValueError("b must hold %d entries of %s" % (n, vt.name))
+    if x is None:
+        if x0_given:
+            raise ValueError("x0_given needs x")
+        x = DeviceArray(n, vt)
+    elif x.dtype != vt or x.n < n:
+        raise ValueError("x must hold %d entries of %s" % (n, vt.name))
+    hist = None
+    if history:
+        cap = int(max_iter) if max_iter else min(n, 1 << 20)
+        hist = np.zeros(max(cap, 1), np.float64)
+    return x, hist
+
+
+def gmres_solve(A, b, precond=None, op="N", restart=30, max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+    """Solves op(A) * x = b on the device by restarted GMRES (bmsp_gmres_solve): right-preconditioned GMRES(restart), restart 1 .. 256
+    (0: 30), the basis orthogonalised by classical Gram-Schmidt applied twice.  One product and one preconditioner application per
+    iteration, plus one product per restart.  Everything else -- A, b, precond, op, max_iter, tol, KRYLOV_NO_CHECK, x, x0_given, history,
+    stream and the results -- is krylov_solve's; info["method"] is "gmres(<m>)+<preconditioner>"."""
+    pc, keep = _precond(precond)
+    i = A.info()
+    x, hist = _solve_vectors(i["num_rows"], np.dtype(OUT_DTYPE[i["dtype"]]), b, x, x0_given, max_iter, history)
+    info = KrylovInfo()
+    check(lib().bmsp_gmres_solve(A.h, _op(op), C.byref(pc) if pc is not None else None, int(restart), b.ptr, x.ptr, int(max_iter),
+                                 float(tol), KRYLOV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info),
+                                 stream))
+    del keep
+    d = info.as_dict()
+    return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+
+
 class Multigrid:
     """The V-cycle of a hierarchy on the device (bmsp_mg_create): A a list of `levels` square BmSpMatrix (F32 or F64, one dtype), P a list
     of levels - 1 prolongators (n_l x n_{l+1}), R None (restrict by P^T) or a list of restrictions / None entries, coarse_inv None or the
@@ -1219,10 +1272,18 @@ class Multigrid:
         check(lib().bmsp_mg_vcycle(self.h, r.ptr, z.ptr, stream))
         return z
 
-    def solve(self, b, method="cg", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
-        """A[0] * x = b by CG or BiCGStab preconditioned by one cycle (bmsp_mg_solve): krylov_solve's arguments and results"""
+    def solve(self, b, method="cg", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None, restart=30):
+        """A[0] * x = b by CG or BiCGStab preconditioned by one cycle (bmsp_mg_solve): krylov_solve's arguments and results.  method
+        "gmres": GMRES(restart) preconditioned by one cycle (bmsp_mg_solve_gmres), which takes any cycle"""
+        if method == "gmres":
+            x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
+            info = KrylovInfo()
+            check(lib().bmsp_mg_solve_gmres(self.h, int(restart), b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
+                                            hist.ctypes.data if history else None, C.byref(info), stream))
+            d = info.as_dict()
+            return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
         if method not in _METHODS:
-            raise ValueError("method must be 'cg' or 'bicgstab' (got %r)" % (method,))
+            raise ValueError("method must be 'cg', 'bicgstab' or 'gmres' (got %r)" % (method,))
         if b.dtype != self.dtype or b.n < self.n:
             raise ValueError("b must hold %d entries of %s" % (self.n, self.dtype.name))
         if x is None:

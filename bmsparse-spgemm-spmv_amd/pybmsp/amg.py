@@ -12,7 +12,8 @@ then grows with the grid, which the hierarchy exists to prevent.  The small host
 roots of the aggregate sizes (and of the diagonal when theta != 0).
 
 The cycle and the solve driven from Python here (vcycle, pcg) are the yardstick; device_cycle hands the same hierarchy to the library's
-enqueued cycle (pybmsp.Multigrid: bmsp_mg_vcycle, bmsp_mg_solve), and tools/amg_bench.py times the two against each other."""
+enqueued cycle (pybmsp.Multigrid: bmsp_mg_vcycle, bmsp_mg_solve with CG or BiCGStab, bmsp_mg_solve_gmres with GMRES for a cycle or a
+matrix that is not symmetric), and tools/amg_bench.py times the two against each other."""
 import numpy as np
 
 import pybmsp as B

@@ -392,6 +392,17 @@ inline void bmSparse_solve(bmSpMatrix<ValueIn> &A, int op, int method, const bms
     bmsp::check(bmsp_krylov_solve(A.handle(), op, method, pc, b, x, max_iter, tol, flags, relres_history, info, nullptr));
     bmsp::check(bmsp_synchronize());
 }
+/* Restarted GMRES (bmsp_gmres_solve): bmSparse_solve's arguments with the restart length (0: 30, at most 256) where the method stood; one
+ * product and one preconditioner application per iteration, no recurrence to break down, for matrices that are not symmetric. */
+template <class ValueIn>
+inline void bmSparse_solve_gmres(bmSpMatrix<ValueIn> &A, int op, const bmsp_precond *pc, int restart,
+                                 const typename bmsp::vector_of<ValueIn>::type *b, typename bmsp::vector_of<ValueIn>::type *x,
+                                 int64_t max_iter = 0, double tol = 1e-6, int flags = 0, double *relres_history = nullptr,
+                                 bmsp_krylov_info *info = nullptr)
+{
+    bmsp::check(bmsp_gmres_solve(A.handle(), op, pc, restart, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+    bmsp::check(bmsp_synchronize());
+}
 template <class R>
 inline double bmSparse_vec_dot(int64_t n, const R *x, const R *y)
 {
@@ -439,6 +450,13 @@ public:
                double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
     {
         bmsp::check(bmsp_mg_solve(h_, method, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+    // GMRES(restart) preconditioned by one cycle (bmsp_mg_solve_gmres): any cycle, symmetric or not
+    void solve_gmres(int restart, const vectorType *b, vectorType *x, int64_t max_iter = 0, double tol = 1e-6, int flags = 0,
+                     double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
+    {
+        bmsp::check(bmsp_mg_solve_gmres(h_, restart, b, x, max_iter, tol, flags, relres_history, info, nullptr));
         bmsp::check(bmsp_synchronize());
     }
 };

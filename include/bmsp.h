@@ -829,6 +829,52 @@ int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *p
                       int64_t max_iter, double tol, int flags, double *relres_history /* host, may be NULL */,
                       bmsp_krylov_info *info /* may be NULL */, void *stream);
 
+/* Restarted GMRES on the device: op(A) x = b for a square A in either tile layout by right-preconditioned GMRES(m), m = restart (0 means
+ * 30, at most 256), with the whole iteration enqueued on `stream` as in bmsp_krylov_solve.  One product and one preconditioner application
+ * per iteration (plus one product per restart), a residual that never grows, and no rho / omega recurrence to break down: the method for
+ * matrices that are not symmetric.  Nothing in the reference is replaced (it has no solver).
+ *   Carried over from bmsp_krylov_solve, word for word: the operands, the preconditioner kinds and their op-T order, max_iter == 0,
+ *       BMSP_KRYLOV_NO_CHECK, BMSP_KRYLOV_X0_GIVEN, the BMSP_KRYLOV_CHECK ramp, the refusals (scalars before handles, the message naming
+ *       the argument), bmsp_precond, bmsp_krylov_info and every define.  New: restart < 0 or restart > 256 is refused, the message
+ *       naming restart.
+ *   Arithmetic, fixed operation by operation.  R is the vector type; scalars are doubles on the device; a scalar is rounded once to R
+ *       (suffix R) before it touches a vector; nothing is contracted; dots are bmsp_vec_dot's.
+ *       Start: exactly bmsp_krylov_solve's -- bb, thr, bb == 0, x0, r = fl(b - op(A) x0) and the rule for the initial residual.
+ *       Cycle start: the residual is r and rr = dot(r, r).  From the second cycle on rr is tested: not finite: BMSP_KRYLOV_BREAKDOWN; rr <=
+ *           thr: BMSP_KRYLOV_CONVERGED, with no record added and info->relres reporting this rr; under BMSP_KRYLOV_NO_CHECK rr == 0:
+ *           BMSP_KRYLOV_BREAKDOWN.  Then beta = sqrt(rr), s = 1.0 / beta, v_0 = fl(sR * r), g_0 = beta.
+ *       Step j = 0 .. m - 1 (iteration k): z_j = M^-1 v_j (z_j is v_j without a preconditioner); w = op(A) z_j.  Two passes p = 1, 2 of
+ *           classical Gram-Schmidt: t_i = dot(v_i, w) for i = 0 .. j, all taken of the same w; then per element, for i ascending,
+ *           w = fl(w - fl(tR_i * v_i)).  h_i = the first pass's t_i + the second pass's t_i, one add; h_{j+1} = sqrt(dot(w, w)).  A t or h that is not
+ *           finite: BMSP_KRYLOV_BREAKDOWN.  The earlier rotations i < j in ascending order, on (a, b) = (h_i, h_{i+1}): h_i = fl(fl(c_i a) +
+ *           fl(s_i b)), h_{i+1} = fl(fl(c_i b) - fl(s_i a)).  The new rotation: d = sqrt(fl(fl(h_j h_j) + fl(h_{j+1} h_{j+1}))) (not hypot); d
+ *           zero or not finite: BMSP_KRYLOV_BREAKDOWN; c_j = h_j / d, s_j = h_{j+1} / d, h_j = d; g_{j+1} = -fl(s_j g_j), g_j = fl(c_j g_j).
+ *           rr_k = fl(g_{j+1} g_{j+1}) is recorded; then not finite: BMSP_KRYLOV_BREAKDOWN; rr_k <= thr: BMSP_KRYLOV_CONVERGED; under
+ *           BMSP_KRYLOV_NO_CHECK rr_k == 0: BMSP_KRYLOV_BREAKDOWN; k == max_iter ends the solve with BMSP_KRYLOV_MAXITER.  Otherwise, for j < m
+ *           - 1, v_{j+1} = fl(sR * w) with s = 1.0 / h_{j+1}.
+ *       End of a cycle with J columns completed (m, or fewer when the rule or the cap stopped it): the back substitution in double, for i =
+ *           J - 1 .. 0: s = g_i; for l = i + 1 .. J - 1 ascending s = fl(s - fl(U_il y_l)); y_i = s / U_ii (U the rotated columns).  Then per
+ *           element, for i ascending, x = fl(x + fl(yR_i * z_i)).  On BMSP_KRYLOV_BREAKDOWN x is NOT updated from the partial cycle: it keeps
+ *           the iterate of the last completed cycle, which is the last iterate written.  If the solve goes on: r = fl(b - op(A) x), rr =
+ *           dot(r, r).
+ *       What the definitions allow is fused (the update of the second pass carries the partial sums of dot(w, w)); the bits are those
+ *       of the text.  x, iterations, status and the history are a pure function of the inputs wherever the product is one.
+ *   Kernels: one launch forms up to BMSP_GMRES_GROUP=<vectors> (1 .. 16, read per call; default 8) of the dots t_i from one read of w, each
+ *       with bmsp_vec_dot's tree, second level by ticket up to 384 chunks and by a launch beyond (BMSP_VEC_DOT_FINISH is honoured); one
+ *       launch applies all of them.  The group never changes the bits.
+ *   Device-resident protocol: bmsp_krylov_solve's.  Every kernel reads the status first and returns without writing once the solve has
+ *       stopped, except the formation of x for the cycle the stop fell into, which still happens, once.  x, iterations, status and the
+ *       history never depend on BMSP_KRYLOV_CHECK, on BMSP_GMRES_GROUP or on the stream.  A BMSP_KRYLOV_NO_CHECK call reads nothing back.
+ *   Results: as bmsp_krylov_solve.  relres_history[k] = sqrt(rr_{k+1} / bb).  info->method is "gmres(<m>)+none" / "+jacobi" / "+ilu" /
+ *       "+ilu_sweeps"; products = the iterations plus the restarts performed (plus one with x0); precond_applies = the iterations (0 for
+ *       none).
+ *   Workspace: the one bmsp_krylov_solve keeps on A's handle, grown by the same rule: m' + 1 basis vectors with m' = min(m, max_iter), m' vectors
+ *       z_j when there is a preconditioner, one vector between the two solves of the ILU kinds, the diagonal, the rotated Hessenberg columns, the
+ *       rotations, g, y, the dots, the dot partials and the records. */
+int bmsp_gmres_solve(bmsp_matrix_t A, int op, const bmsp_precond *pc /* NULL = none */, int restart /* 0 = 30 */,
+                     const void *d_b, void *d_x, int64_t max_iter, double tol, int flags, double *relres_history,
+                     bmsp_krylov_info *info, void *stream);
+
 /* Multigrid on the device: the V-cycle of a hierarchy the caller supplies (pybmsp/amg.py's smoothed aggregation, a geometric one, any),
  * enqueued on a stream like the rest of bmsp_krylov_solve, and CG / BiCGStab for A[0] * x = b preconditioned by one cycle.  The cycle is
  * not a `kind` of bmsp_krylov_solve (bmsp_precond is fixed): it has its own handle and its own solve.  Nothing in the reference is
@@ -902,6 +948,11 @@ int bmsp_mg_info(bmsp_mg_t mg, bmsp_mg_info_t *info);
 int bmsp_mg_vcycle(bmsp_mg_t mg, const void *d_r, void *d_z, void *stream);
 int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
                   double *relres_history, bmsp_krylov_info *info, void *stream);
+/* bmsp_gmres_solve(A[0], BMSP_OP_N, ., restart, ...) with z_j = M^-1 v_j one cycle: its arithmetic, rules, modes, results and refusals;
+ * info->method is "gmres(<m>)+mg".  Takes any cycle, symmetric or not.  The views for the restriction are built before the first
+ * iteration is enqueued, and the cycle's kernels read the solver's status word first, as in bmsp_mg_solve. */
+int bmsp_mg_solve_gmres(bmsp_mg_t mg, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                        double *relres_history, bmsp_krylov_info *info, void *stream);
 
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]

@@ -24,6 +24,8 @@ where a hub row is one lane's serial walk.  Per matrix:
                      cg          Multigrid.solve CG against amg.pcg: to TOL where CG applies, and both at a fixed 50 iterations
                                  (tol = 0) for the time per iteration on every matrix
                      bicgstab    Multigrid.solve BiCGStab to TOL (the method for the matrices that are not symmetric)
+                     gmres       Multigrid.solve GMRES(--restart) to TOL: one cycle per iteration where BiCGStab takes two
+  --gmres            only the solves: BiCGStab and GMRES(--restart) under Jacobi and under the cycle (no aggregation, stage or crossover rows)
   restrict_crossover   the restriction on synthetic operators of 12 / 24 / 48 / 96 tiles per block-row of R, row mode under each walk
                    against spmv mode: where the default rule's threshold comes from
 Prints one JSON line."""
@@ -105,10 +107,26 @@ def spread(fn, inner=1, runs=5):
     return {"ms": round(statistics.median(t), 4), "min": round(min(t), 4), "max": round(max(t), 4)}
 
 
+def bench_krylov_on_cycle(mg, n, b, setup_ms, create, a):
+    """BiCGStab and GMRES(--restart) preconditioned by one cycle, to TOL: the two methods for matrices that are not symmetric"""
+    out = {}
+    x = B.DeviceArray(n, np.float32)
+    for label, run in (("bicgstab", lambda: mg.solve(b, "bicgstab", a.cap, TOL, x)),
+                       ("gmres", lambda: mg.solve(b, "gmres", a.cap, TOL, x, restart=a.restart))):
+        run()
+        info = run()[1]
+        out[label] = {"iterations": info["iterations"], "status": info["status"], "relres": info["relres"], "products": info["products"],
+                      "precond_applies": info["precond_applies"], **spread(run)}
+        out[label]["time_to_solution_ms"] = round(out[label]["ms"] + setup_ms + create, 3)
+    return out
+
+
 def bench_multigrid(A, levels, method, n, b, setup_ms, a):
     from pybmsp import amg
     out = {}
     mg, create = wall_ms(lambda: amg.device_cycle(levels))
+    if a.gmres:
+        return bench_krylov_on_cycle(mg, n, b, setup_ms, create, a)
     info = mg.info()
     out["create_ms"] = create
     out["info"] = {k: info[k] for k in ("n", "restrict_mode", "launches_per_cycle", "workspace_bytes", "kernel", "coarse_kernel")}
@@ -169,11 +187,7 @@ def bench_multigrid(A, levels, method, n, b, setup_ms, a):
                          "device_ms_per_iteration": round(d["ms"] / max(d_it, 1), 4), "python_ms_per_iteration": round(p["ms"] / max(p_it, 1), 4)}
     out["cg_fixed50"]["python_over_device_per_iteration"] = round(out["cg_fixed50"]["python_ms_per_iteration"] /
                                                                   max(out["cg_fixed50"]["device_ms_per_iteration"], 1e-9), 2)
-    run2 = lambda: mg.solve(b, "bicgstab", a.cap, TOL, x)
-    run2()
-    info = run2()[1]
-    out["bicgstab"] = {"iterations": info["iterations"], "status": info["status"], "relres": info["relres"], **spread(run2)}
-    out["bicgstab"]["time_to_solution_ms"] = round(out["bicgstab"]["ms"] + setup_ms + create, 3)
+    out.update(bench_krylov_on_cycle(mg, n, b, setup_ms, create, a))
     return out
 
 
@@ -222,6 +236,15 @@ def bench_amg(A, method, n, a):
     levels, setup = wall_ms(lambda: amg.build_hierarchy(A, coarse=a.coarse))
     out = {"levels": [lv.n for lv in levels], "rounds": [lv.info["rounds"] for lv in levels if lv.info], "setup_first_ms": setup,
            "setup_ms": median_wall_ms(lambda: amg.build_hierarchy(A, coarse=a.coarse), max(1, a.reps // 2))}
+    if a.gmres:
+        x = B.DeviceArray(n, np.float32)
+        for label, run in (("bicgstab_jacobi", lambda: B.krylov_solve(A, b, "bicgstab", "jacobi", x=x, max_iter=a.cap, tol=TOL)),
+                           ("gmres_jacobi", lambda: B.gmres_solve(A, b, "jacobi", restart=a.restart, x=x, max_iter=a.cap, tol=TOL))):
+            run()
+            info = run()[1]
+            out[label] = {"iterations": info["iterations"], "status": info["status"], "relres": info["relres"], "ms": median_wall_ms(run, a.reps)}
+        out["multigrid"] = bench_multigrid(A, levels, method, n, b, out["setup_ms"], a)
+        return out
     amg.pcg(A, b, levels, tol=TOL, max_iter=20)                                    # warm-up
     (_, info), ms = wall_ms(lambda: amg.pcg(A, b, levels, tol=TOL, max_iter=a.cap))
     out["vcycle_pcg"] = dict(info, ms=ms, time_to_solution_ms=round(ms + out["setup_ms"], 3))
@@ -245,6 +268,8 @@ def main():
     ap.add_argument("--coarse", type=int, default=200)
     ap.add_argument("--only", default="")
     ap.add_argument("--small", action="store_true", help="small shapes (a quick check of the tool itself)")
+    ap.add_argument("--gmres", action="store_true", help="only the solves: BiCGStab and GMRES(--restart) under Jacobi and under the cycle")
+    ap.add_argument("--restart", type=int, default=30)
     a = ap.parse_args()
     B.set_device(0)
     if a.small:
@@ -265,14 +290,15 @@ def main():
             r, c, v = with_dominant_diagonal(n, r, c, v)
         A = B.BmSpMatrix.from_coo(n, n, r, c, v, dtype=B.F32)
         row = {"matrix": name, "method": method, "rows": n, "nnz": A.info()["nnz"], "tiles": A.info()["block_num"]}
-        agg, num, row["aggregate"] = bench_aggregate(A, a)
-        row["from_aggregates"] = bench_from_aggregates(agg, num, n, a)
+        if not a.gmres:
+            agg, num, row["aggregate"] = bench_aggregate(A, a)
+            row["from_aggregates"] = bench_from_aggregates(agg, num, n, a)
         if whole:
             row["amg"] = bench_amg(A, method, n, a)
         rows.append(row)
         print("row " + json.dumps(rows[-1]), file=sys.stderr, flush=True)          # (progress; the result is the one line on stdout)
     out = {"tool": "amg_bench", "dtype": "fp32", "tol": TOL, "rows": rows}
-    if not a.only or "crossover" in a.only.split(","):
+    if not a.gmres and (not a.only or "crossover" in a.only.split(",")):
         out["restrict_crossover"] = bench_restrict_crossover(a)
     print(json.dumps(out))
 

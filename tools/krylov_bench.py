@@ -16,6 +16,12 @@ under each preconditioner: none, jacobi, ilu (bmsp_spsv on the factor at its fix
   host_loop                    the route a user had before: the same algorithm driven from Python -- the library's calls for products and
                                preconditioners, torch for dots and updates, one .item() per iteration: iterations, total and per iteration
                                (wall clock; not for ilu, whose solves dominate either way)
+--gmres times bmsp_gmres_solve instead: GMRES(--restart) against BiCGStab with the same preconditioner on all five matrices, the checked
+call at the default read-back schedule (iterations, status, relres, call_us, time_to_solution_ms; iter_us of GMRES from NO_CHECK runs of
+one and of two full cycles).  --ortho times the orthogonalisation: one iteration of GMRES at basis size j + 1 on a diagonal matrix
+(t(j + 1 iterations) - t(j iterations) under NO_CHECK, the median of 8 * reps + 1 back-to-back pairs: the product of one entry per row, two passes of dots and updates, the scalar
+kernel, the normalisation) under BMSP_GMRES_GROUP in {4, 8, 16}, against the same two passes assembled from public calls -- j + 1
+bmsp_vec_dot and j + 1 bmsp_vec_axpby each -- for j in {7, 15, 29} and n in {2^18, 2^21}, fp32.
 Prints one JSON line."""
 import argparse
 import json
@@ -182,8 +188,86 @@ def bench(name, method, n, r, c, v, dtype, a, torch):
     return row
 
 
+def bench_gmres(name, n, r, c, v, dtype, a):
+    R = np.float64 if dtype == B.F64 else np.float32
+    A = B.BmSpMatrix.from_coo(n, n, r, c, v, dtype=dtype)
+    row = {"matrix": name, "dtype": "fp64" if dtype == B.F64 else "fp32", "rows": n, "nnz": A.info()["nnz"], "restart": a.restart, "pc": {}}
+    hb = np.random.default_rng(7).uniform(-1.0, 1.0, n).astype(R)
+    b, x = B.DeviceArray.from_host(hb), B.DeviceArray(n, R)
+    sweeps6, t6 = wall_ms(lambda: B.ilu0(A, max_iter=6, tol=B.ILU_NO_CHECK)[0])
+    (fixed, finfo), tfix = wall_ms(lambda: B.ilu0(A, max_iter=a.fixed_cap, tol=0.0))
+    kinds = [("none", None, 0.0, a.cap), ("jacobi", "jacobi", 0.0, a.cap)]
+    kinds += [("ilu_sweeps%d" % m, ("ilu_sweeps", sweeps6, m), t6, a.cap) for m in (2, 4, 8)]
+    kinds += [("ilu", ("ilu", fixed), tfix, a.exact_cap)]
+    set_check(None)
+    for label, pc, setup, cap in kinds:
+        per = {"setup_ms": setup}
+        for method, run in (("bicgstab", lambda **kw: B.krylov_solve(A, b, "bicgstab", pc, x=x, **kw)),
+                            ("gmres", lambda **kw: B.gmres_solve(A, b, pc, restart=a.restart, x=x, **kw))):
+            (_, info), first_ms = wall_ms(lambda: run(max_iter=cap, tol=TOL))      # (builds plans and views)
+            m = {"iterations": info["iterations"], "status": info["status"], "relres": info["relres"], "products": info["products"],
+                 "precond_applies": info["precond_applies"]}
+            m["call_us"] = round(first_ms * 1e3, 1) if label == "ilu" else event_us(lambda: run(max_iter=cap, tol=TOL), a.reps)
+            if method == "gmres" and label != "ilu":
+                t1 = event_us(lambda: run(max_iter=a.restart, tol=B.KRYLOV_NO_CHECK), a.reps)
+                t2 = event_us(lambda: run(max_iter=2 * a.restart, tol=B.KRYLOV_NO_CHECK), a.reps)
+                m["iter_us"] = round((t2 - t1) / a.restart, 2)                      # (the mean over a cycle, its restart included)
+            m["time_to_solution_ms"] = round(setup + m["call_us"] / 1e3, 3)
+            per[method] = m
+        row["pc"][label] = per
+    return row
+
+
+def paired_us(short, long, pairs):
+    """median over `pairs` of t(long) - t(short), the two timed back to back with HIP events"""
+    e = [B.Event() for _ in range(3)]
+    short(), long()
+    B.synchronize()
+    d = []
+    for _ in range(pairs):
+        e[0].record()
+        short()
+        e[1].record()
+        long()
+        e[2].record()
+        B.synchronize()
+        d.append((e[1].elapsed_ms(e[2]) - e[0].elapsed_ms(e[1])) * 1e3)
+    return round(statistics.median(d), 1)
+
+
+def bench_ortho(a):
+    rows = []
+    for n in (1 << 18, 1 << 21):
+        e = np.arange(n)
+        A = B.BmSpMatrix.from_coo(n, n, e, e, np.full(n, 1.5), dtype=B.F32)
+        rng = np.random.default_rng(3)
+        b, x = B.DeviceArray.from_host(rng.uniform(-1.0, 1.0, n).astype(np.float32)), B.DeviceArray(n, np.float32)
+        w = B.DeviceArray.from_host(rng.uniform(-1.0, 1.0, n).astype(np.float32))
+        out = B.DeviceArray(1, np.float64)
+        run = lambda m: B.gmres_solve(A, b, None, restart=32, max_iter=m, tol=B.KRYLOV_NO_CHECK, x=x)
+        run(32)
+        for j in (7, 15, 29):
+            def public():
+                for _ in range(2):
+                    for _ in range(j + 1):
+                        B.vec_dot(b, w, out=out)
+                    for _ in range(j + 1):
+                        B.vec_axpby(-1e-3, b, 1.0, w)
+            row = {"n": n, "j": j, "public_calls_us": event_us(public, a.reps, 2), "gmres_step_us": {}}
+            for group in ("4", "8", "16"):
+                os.environ["BMSP_GMRES_GROUP"] = group
+                row["gmres_step_us"][group] = paired_us(lambda: run(j), lambda: run(j + 1), 8 * a.reps + 1)
+            os.environ.pop("BMSP_GMRES_GROUP", None)
+            rows.append(row)
+            print("row " + json.dumps(row), file=sys.stderr, flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gmres", action="store_true", help="GMRES(--restart) against BiCGStab, time to solution")
+    ap.add_argument("--ortho", action="store_true", help="the orthogonalisation step against public calls")
+    ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cap", type=int, default=2000)
     ap.add_argument("--exact-cap", type=int, default=40)
@@ -199,6 +283,9 @@ def main():
     except ImportError:
         torch = None
     B.set_device(0)
+    if a.ortho:
+        print(json.dumps({"tool": "krylov_bench", "mode": "ortho", "rows": bench_ortho(a)}))
+        return
     if a.small:
         mats = [("poisson27_8", "cg", lambda: gen.poisson("27pt", 8, 8, 8), False), ("banded_small", "bicgstab", lambda: gen.banded(1 << 10, 8), True)]
     else:
@@ -214,6 +301,10 @@ def main():
         if dominant:
             r, c, v = with_dominant_diagonal(n, r, c, v)
         for dt in a.dtypes.split(","):
+            if a.gmres:
+                rows.append(bench_gmres(name, n, r, c, v, B.F64 if dt == "fp64" else B.F32, a))
+                print("row " + json.dumps(rows[-1]), file=sys.stderr, flush=True)
+                continue
             rows.append(bench(name, method, n, r, c, v, B.F64 if dt == "fp64" else B.F32, a, torch))
             print("row " + json.dumps(rows[-1]), file=sys.stderr, flush=True)          # (progress; the result is the one line on stdout)
     print(json.dumps({"tool": "krylov_bench", "tol": TOL, "check_default": "1, 2, 4, 8, then 16 per batch", "torch": torch is not None, "rows": rows}))
