@@ -934,6 +934,108 @@ int bmsp_mg_solve_gmres(bmsp_mg_t mg, int restart, const void *d_b, void *d_x, i
     BMSP_API_END
 }
 
+int bmsp_matrix_fsai(bmsp_matrix_t A, int op, bmsp_matrix_t S, int scale, int out_transposed, void *d_pivot, void *stream, bmsp_matrix_t *out,
+                     bmsp_fsai_info *info)
+{
+    BMSP_API_BEGIN
+    fsai_check_args(op, scale, out_transposed);
+    need(A, "matrix A"); need(S, "matrix S"); need(out, "out"); need(info, "info");
+    fsai_check_matrices(A, S, "S");
+    load_kernels();
+    bmsp_matrix_s *G = fsai_matrix(A, op, S, scale, out_transposed, d_pivot, as_stream(stream), info);
+    *out = G;
+    BMSP_API_END
+}
+
+int bmsp_matrix_fsai_values(bmsp_matrix_t A, int op, bmsp_matrix_t G, int scale, void *d_pivot, void *stream, bmsp_fsai_info *info)
+{
+    BMSP_API_BEGIN
+    fsai_check_args(op, scale, 0);
+    need(A, "matrix A"); need(G, "matrix G"); need(info, "info");
+    fsai_check_matrices(A, G, "G");
+    load_kernels();
+    fsai_values_into(A, op, G, scale, d_pivot, as_stream(stream), info);
+    BMSP_API_END
+}
+
+int bmsp_fsai_create(bmsp_matrix_t A, bmsp_matrix_t S, int kind, int flags, void *stream, bmsp_fsai_t *out)
+{
+    BMSP_API_BEGIN
+    fsai_create_check_args(kind, flags);
+    need(A, "matrix A"); need(S, "matrix S"); need(out, "out");
+    fsai_check_matrices(A, S, "S");
+    load_kernels();
+    bmsp_fsai_s *f = fsai_create(A, S, kind, flags, as_stream(stream));
+    *out = f;
+    BMSP_API_END
+}
+
+int bmsp_fsai_update(bmsp_fsai_t f, void *stream)
+{
+    BMSP_API_BEGIN
+    need(f, "f");
+    load_kernels();
+    fsai_update(f, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_fsai_free(bmsp_fsai_t f)
+{
+    BMSP_API_BEGIN
+    fsai_free(f);
+    BMSP_API_END
+}
+
+int bmsp_fsai_get_info(bmsp_fsai_t f, bmsp_fsai_handle_info *info)
+{
+    BMSP_API_BEGIN
+    need(f, "f"); need(info, "info");
+    fsai_get_info(f, info);
+    BMSP_API_END
+}
+
+int bmsp_fsai_factors(bmsp_fsai_t f, bmsp_matrix_t *G1, bmsp_matrix_t *G2)
+{
+    BMSP_API_BEGIN
+    need(f, "f");
+    fsai_factors(f, G1, G2);
+    BMSP_API_END
+}
+
+int bmsp_fsai_apply(bmsp_fsai_t f, const void *d_r, void *d_z, void *stream)
+{
+    BMSP_API_BEGIN
+    need(f, "f"); need(d_r, "d_r"); need(d_z, "d_z");
+    if (d_r == d_z) fail(BMSP_ERR_INVALID, "d_z must not be d_r");
+    load_kernels();
+    fsai_apply(f, d_r, d_z, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_fsai_solve(bmsp_fsai_t f, int method, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags, double *relres_history,
+                    bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    krylov_check_args(BMSP_OP_N, method, nullptr, max_iter, tol, flags, relres_history);
+    need(f, "f"); need(d_b, "d_b"); need(d_x, "d_x");
+    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    load_kernels();
+    fsai_solve(f, method, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
+int bmsp_fsai_solve_gmres(bmsp_fsai_t f, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                          double *relres_history, bmsp_krylov_info *info, void *stream)
+{
+    BMSP_API_BEGIN
+    gmres_check_args(BMSP_OP_N, restart, nullptr, max_iter, tol, flags, relres_history);
+    need(f, "f"); need(d_b, "d_b"); need(d_x, "d_x");
+    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    load_kernels();
+    fsai_solve_gmres(f, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    BMSP_API_END
+}
+
 int bmsp_spsv_plan(const uint32_t *ptr, const uint32_t *other, int64_t blocks, int lower, int64_t chain, uint32_t *level_of, uint32_t *order,
                    uint32_t *level_ptr, uint32_t *segments, int64_t *n_levels, int64_t *n_segments)
 {

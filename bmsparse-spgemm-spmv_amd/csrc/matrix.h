@@ -426,6 +426,25 @@ void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_ite
               bmsp_krylov_info *info, hipStream_t st);
 void mg_solve_gmres(bmsp_mg_s *mg, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
                     bmsp_krylov_info *info, hipStream_t st);
+// fsai.hip: the factorised sparse approximate inverse of op(A) on S's lower-triangular pattern as a new matrix (tiles in layout
+// out_transposed) or into a matrix G with a legal pattern (both synchronise `st`), and the preconditioner handle z = G2^T (G1 r) by two
+// bmsp_spmv_op, with CG / BiCGStab / GMRES for A x = b on top.  fsai_create and fsai_update synchronise `st`.
+void fsai_check_args(int op, int scale, int out_transposed);
+void fsai_check_matrices(const bmsp_matrix_s *A, const bmsp_matrix_s *P, const char *name);
+bmsp_matrix_s *fsai_matrix(bmsp_matrix_s *A, int op, bmsp_matrix_s *S, int scale, int out_transposed, void *d_pivot, hipStream_t st,
+                           bmsp_fsai_info *info);
+void fsai_values_into(bmsp_matrix_s *A, int op, bmsp_matrix_s *G, int scale, void *d_pivot, hipStream_t st, bmsp_fsai_info *info);
+void fsai_create_check_args(int kind, int flags);
+bmsp_fsai_s *fsai_create(bmsp_matrix_s *A, bmsp_matrix_s *S, int kind, int flags, hipStream_t st);
+void fsai_update(bmsp_fsai_s *f, hipStream_t st);
+void fsai_free(bmsp_fsai_s *f);
+void fsai_get_info(bmsp_fsai_s *f, bmsp_fsai_handle_info *info);
+void fsai_factors(bmsp_fsai_s *f, bmsp_matrix_s **G1, bmsp_matrix_s **G2);
+void fsai_apply(bmsp_fsai_s *f, const void *r, void *z, hipStream_t st);
+void fsai_solve(bmsp_fsai_s *f, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+                bmsp_krylov_info *info, hipStream_t st);
+void fsai_solve_gmres(bmsp_fsai_s *f, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
+                      bmsp_krylov_info *info, hipStream_t st);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

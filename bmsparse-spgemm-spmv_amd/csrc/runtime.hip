@@ -201,6 +201,7 @@ void warm_gmres(hipStream_t st);
 void warm_reorder(hipStream_t st);
 void warm_aggregate(hipStream_t st);
 void warm_multigrid(hipStream_t st);
+void warm_fsai(hipStream_t st);
 
 void *host_slot_acquire();
 void host_slot_release(void *p);
@@ -246,6 +247,7 @@ void load_kernels()
     warm_reorder(nullptr);
     warm_aggregate(nullptr);
     warm_multigrid(nullptr);
+    warm_fsai(nullptr);
     // the first pinned host page and the first device-to-host copy of a process cost ~15 ms (measured inside the first product's T_1):
     // taken here too, with a copy through the slot
     // ... and so does the first timed event of a process (the stage timers' events; the queue is switched to profiling)

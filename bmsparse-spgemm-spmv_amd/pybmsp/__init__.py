@@ -38,7 +38,12 @@ KRYLOV_NO_CHECK = -1.0
 KRYLOV_MAXITER, KRYLOV_CONVERGED, KRYLOV_BREAKDOWN = 0, 1, 2
 MG_MAX_LEVELS = 16
 MG_RESTRICT_ROW, MG_RESTRICT_SPMV, MG_RESTRICT_PT = 0, 1, 2
+FSAI_SCALE_NONE, FSAI_SCALE_SQRT, FSAI_SCALE_UNIT = 0, 1, 2
+FSAI_SPD, FSAI_GENERAL = 0, 1
+FSAI_NO_MATERIALISE, FSAI_COLMAJOR = 1, 2
 _METHODS = {"cg": KRYLOV_CG, "bicgstab": KRYLOV_BICGSTAB, KRYLOV_CG: KRYLOV_CG, KRYLOV_BICGSTAB: KRYLOV_BICGSTAB}
+_FSAI_SCALES = {"none": FSAI_SCALE_NONE, "sqrt": FSAI_SCALE_SQRT, "unit": FSAI_SCALE_UNIT, 0: 0, 1: 1, 2: 2}
+_FSAI_KINDS = {"spd": FSAI_SPD, "general": FSAI_GENERAL, 0: 0, 1: 1}
 _OPS = {"N": OP_N, "T": OP_T, "n": OP_N, "t": OP_T, OP_N: OP_N, OP_T: OP_T}
 _FILLS = {"lower": FILL_LOWER, "upper": FILL_UPPER, "L": FILL_LOWER, "U": FILL_UPPER, FILL_LOWER: FILL_LOWER, FILL_UPPER: FILL_UPPER}
 _PRUNE_RULES = {"abs": PRUNE_ABS, "row_rel": PRUNE_ROW_REL, PRUNE_ABS: PRUNE_ABS, PRUNE_ROW_REL: PRUNE_ROW_REL}
@@ -53,7 +58,7 @@ SYMBOLS = [
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
     "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
-    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_gmres_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_mg_solve_gmres", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
+    "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_gmres_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_mg_solve_gmres", "bmsp_matrix_fsai", "bmsp_matrix_fsai_values", "bmsp_fsai_create", "bmsp_fsai_update", "bmsp_fsai_free", "bmsp_fsai_get_info", "bmsp_fsai_factors", "bmsp_fsai_apply", "bmsp_fsai_solve", "bmsp_fsai_solve_gmres", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
     "bmsp_comm_unique_id", "bmsp_comm_init", "bmsp_comm_init_from_env", "bmsp_comm_init_loopback", "bmsp_shard_layout", "bmsp_shard_row_slices", "bmsp_comm_info", "bmsp_comm_free", "bmsp_spgemm_sharded", "bmsp_spgemm_sharded_ex", "bmsp_spmv_sharded",
     "bmsp_csr_from_mtx", "bmsp_csr_from_arrays", "bmsp_csr_info", "bmsp_csr_arrays", "bmsp_csr_multiply",
@@ -205,6 +210,25 @@ class MgInfo(C.Structure):
                 "launches_per_cycle": self.launches_per_cycle}
 
 
+class FsaiInfo(C.Structure):
+    _fields_ = [("kernel", C.c_char * 64), ("lanes", C.c_int), ("rows", C.c_int64), ("max_row", C.c_int64), ("pairs", C.c_int64),
+                ("bad_rows", C.c_int64), ("lds_bytes", C.c_int64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kernel"] = self.kernel.decode()
+        return d
+
+
+class FsaiHandleInfo(C.Structure):
+    _fields_ = [("kind", C.c_int), ("flags", C.c_int), ("materialised", C.c_int), ("n", C.c_int64), ("owned_bytes", C.c_int64),
+                ("factor", FsaiInfo * 2)]
+
+    def as_dict(self):
+        return {"kind": self.kind, "flags": self.flags, "materialised": self.materialised, "n": self.n, "owned_bytes": self.owned_bytes,
+                "factor": [self.factor[0].as_dict(), self.factor[1].as_dict()]}
+
+
 class ShardStats(C.Structure):
     _fields_ = [("world", C.c_int), ("rank", C.c_int), ("panel_block_row_begin", C.c_int64), ("panel_block_row_end", C.c_int64),
                 ("panel_tasks", C.c_int64), ("exchange_bytes", C.c_int64), ("exchange_us", C.c_double), ("exchange_exposed_us", C.c_double),
@@ -300,6 +324,16 @@ def lib():
         L.bmsp_mg_vcycle.argtypes = [vp, vp, vp, vp]
         L.bmsp_mg_solve.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_mg_solve_gmres.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_matrix_fsai.argtypes = [vp, i, vp, i, i, vp, vp, p(vp), p(FsaiInfo)]
+        L.bmsp_matrix_fsai_values.argtypes = [vp, i, vp, i, vp, vp, p(FsaiInfo)]
+        L.bmsp_fsai_create.argtypes = [vp, vp, i, i, vp, p(vp)]
+        L.bmsp_fsai_update.argtypes = [vp, vp]
+        L.bmsp_fsai_free.argtypes = [vp]
+        L.bmsp_fsai_get_info.argtypes = [vp, p(FsaiHandleInfo)]
+        L.bmsp_fsai_factors.argtypes = [vp, p(vp), p(vp)]
+        L.bmsp_fsai_apply.argtypes = [vp, vp, vp, vp]
+        L.bmsp_fsai_solve.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
+        L.bmsp_fsai_solve_gmres.argtypes = [vp, i, vp, vp, i64, C.c_double, i, vp, p(KrylovInfo), vp]
         L.bmsp_sddmm.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, i, vp, p(vp)]
         L.bmsp_sddmm_values.argtypes = [vp, vp, i64, vp, i64, i, C.c_double, C.c_double, i, vp, vp]
         L.bmsp_sddmm_launch_info.argtypes = [vp, i, i64, i64, i, p(SddmmInfo)]
@@ -623,6 +657,10 @@ class BmSpMatrix:
     def ilu0(self, max_iter=0, tol=0.0, out_transposed=None, history=False, stream=None):
         """(F, info[, history]): the incomplete factor ILU(0) of this matrix by fixed-point sweeps: pybmsp.ilu0"""
         return ilu0(self, max_iter, tol, out_transposed, history, stream)
+
+    def fsai(self, S, op="N", scale="sqrt", transposed=None, pivot=False, stream=None):
+        """(G, info[, pivot]): the factorised sparse approximate inverse of op(this) on S's lower-triangular pattern: pybmsp.fsai"""
+        return fsai(self, S, op, scale, transposed, pivot, stream)
 
     def solve(self, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
         """(x, info[, history]) with op(this) * x = b by CG or BiCGStab on the device: pybmsp.krylov_solve.  method "gmres" or
@@ -1299,6 +1337,142 @@ class Multigrid:
             hist = np.zeros(max(cap, 1), np.float64)
         check(lib().bmsp_mg_solve(self.h, _METHODS[method], b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
                                   hist.ctypes.data if history else None, C.byref(info), stream))
+        d = info.as_dict()
+        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+
+
+def fsai(A, S, op="N", scale="sqrt", transposed=None, pivot=False, stream=None):
+    """The factorised sparse approximate inverse of op(A) on the pattern of S (bmsp_matrix_fsai): row i of G solves the small dense system
+    on the stored columns of row i of S -- S lower triangular with the diagonal stored, at most 64 entries per row, values ignored -- and
+    is scaled by `scale`: "none" (g = y), "sqrt" (g = y / sqrt(y_m): G A G^T has a unit diagonal) or "unit" (g = y / y_m).  G has S's
+    structure, A's dtype (F32 or F64) and its tiles in layout `transposed` (None: S's layout).  Returns (G, info) or, with pivot=True,
+    (G, info, pivot): the DeviceArray of the n values y_m; info = {"kernel", "lanes", "rows", "max_row", "pairs", "bad_rows",
+    "lds_bytes"}.  Synchronises `stream`."""
+    lay = S.info()["transposed"] if transposed is None else int(bool(transposed))
+    i = A.info()
+    d = DeviceArray(i["num_rows"], OUT_DTYPE[i["dtype"]]) if pivot else None
+    h, info = C.c_void_p(), FsaiInfo()
+    check(lib().bmsp_matrix_fsai(A.h, _op(op), S.h, _FSAI_SCALES[scale], lay, d.ptr if pivot else None, stream, C.byref(h), C.byref(info)))
+    G = BmSpMatrix(h.value)
+    return (G, info.as_dict(), d) if pivot else (G, info.as_dict())
+
+
+def fsai_values(A, G, op="N", scale="sqrt", pivot=False, stream=None):
+    """fsai(A, ...)'s values into an existing G -- made by fsai(), or any matrix of A's shape and dtype with a legal pattern -- after A's
+    values changed (bmsp_matrix_fsai_values).  Returns (G, info) or (G, info, pivot).  Synchronises `stream`."""
+    i = A.info()
+    d = DeviceArray(i["num_rows"], OUT_DTYPE[i["dtype"]]) if pivot else None
+    info = FsaiInfo()
+    check(lib().bmsp_matrix_fsai_values(A.h, _op(op), G.h, _FSAI_SCALES[scale], d.ptr if pivot else None, stream, C.byref(info)))
+    return (G, info.as_dict(), d) if pivot else (G, info.as_dict())
+
+
+class _TorchView:
+    """a DeviceArray seen through __cuda_array_interface__ (no copy)"""
+
+    def __init__(self, d):
+        self.keep = d
+        self.__cuda_array_interface__ = {"shape": (d.n,), "typestr": d.dtype.str, "data": (d.ptr, False), "version": 2}
+
+
+def fsai_pattern(A, theta=0.0, transposed=None, stream=None):
+    """A pattern for fsai(): the lower triangle of A's pattern, after prune(theta, "row_rel", keep_diagonal=True) when theta > 0 (tiles in
+    layout `transposed`; None: A's layout).  Set-up convenience, not hot path: the entries take the COO route on the device and a torch
+    mask (torch must be importable, and imported before this module)."""
+    import torch
+    i = A.info()
+    M = prune(A, float(theta), "row_rel", True, None, stream)[0] if theta > 0 else A
+    lay = i["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    if M.nnz == 0:
+        check(lib().bmsp_matrix_from_coo_device(i["num_rows"], i["num_cols"], 0, None, None, None, lay, i["dtype"], stream, C.byref(h)))
+        return BmSpMatrix(h.value)
+    r, c, v = M.to_coo_device(stream)
+    synchronize()
+    tr, tc, tv = (torch.as_tensor(_TorchView(d), device="cuda") for d in (r, c, v))
+    keep = tc <= tr
+    kr, kc, kv = tr[keep].contiguous(), tc[keep].contiguous(), tv[keep].contiguous()
+    torch.cuda.synchronize()
+    check(lib().bmsp_matrix_from_coo_device(i["num_rows"], i["num_cols"], int(kr.numel()), kr.data_ptr(), kc.data_ptr(), kv.data_ptr(), lay,
+                                            i["dtype"], stream, C.byref(h)))
+    synchronize()
+    return BmSpMatrix(h.value)
+
+
+class Fsai:
+    """The FSAI preconditioner of A on the pattern S (bmsp_fsai_create): kind "spd" -- G = fsai(A, N, S, sqrt), z = G^T (G r), symmetric
+    positive definite, so CG may use it -- or "general" -- z = W^T (L r) with L = fsai(A, N, S, none), W = fsai(A, T, S, unit).  The
+    application is two spmv_op calls; materialise=False applies the second as op T instead of on a materialised transpose, colmajor=True
+    puts every factor in the column-major layout.  The object keeps A alive; S may go after construction."""
+
+    def __init__(self, A, S, kind="spd", materialise=True, colmajor=False, stream=None):
+        self.h = None
+        self._keep = A
+        i = A.info()
+        self.dtype, self.n = np.dtype(OUT_DTYPE[i["dtype"]]), i["num_rows"]
+        flags = (0 if materialise else FSAI_NO_MATERIALISE) | (FSAI_COLMAJOR if colmajor else 0)
+        h = C.c_void_p()
+        check(lib().bmsp_fsai_create(A.h, S.h, _FSAI_KINDS[kind], flags, stream, C.byref(h)))
+        self.h = h.value
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.bmsp_fsai_free(self.h)
+            self.h = None
+
+    def info(self):
+        i = FsaiHandleInfo()
+        check(lib().bmsp_fsai_get_info(self.h, C.byref(i)))
+        return i.as_dict()
+
+    def factors(self):
+        """(G1, G2): the two factors as borrowed BmSpMatrix (G2 is G1 for kind "spd"); they live as long as this object"""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().bmsp_fsai_factors(self.h, C.byref(a), C.byref(b)))
+        out = []
+        for q in (a, b):
+            m = BmSpMatrix(q.value, parent=self)
+            m.free = lambda: None  # (lent: the handle frees it)
+            out.append(m)
+        return tuple(out)
+
+    def update(self, stream=None):
+        """new factor values after a value update of A (bmsp_fsai_update)"""
+        check(lib().bmsp_fsai_update(self.h, stream))
+        return self
+
+    def apply(self, r, z=None, stream=None):
+        """z = G2^T (G1 r) (DeviceArrays of the vector type; z is made when None), asynchronous on `stream`"""
+        if r.dtype != self.dtype or r.n < self.n:
+            raise ValueError("r must hold %d entries of %s" % (self.n, self.dtype.name))
+        if z is None:
+            z = DeviceArray(self.n, self.dtype)
+        elif z.dtype != self.dtype or z.n < self.n:
+            raise ValueError("z must hold %d entries of %s" % (self.n, self.dtype.name))
+        check(lib().bmsp_fsai_apply(self.h, r.ptr, z.ptr, stream))
+        return z
+
+    def solve(self, b, method="cg", max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+        """A x = b by CG or BiCGStab preconditioned by this (bmsp_fsai_solve): krylov_solve's arguments and results; method "gmres" or
+        "gmres(<m>)" goes to solve_gmres"""
+        restart = _gmres_restart(method)
+        if restart is not None:
+            return self.solve_gmres(b, restart, max_iter, tol, x, x0_given, history, stream)
+        if method not in _METHODS:
+            raise ValueError("method must be 'cg', 'bicgstab' or 'gmres' (got %r)" % (method,))
+        x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
+        info = KrylovInfo()
+        check(lib().bmsp_fsai_solve(self.h, _METHODS[method], b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
+                                    hist.ctypes.data if history else None, C.byref(info), stream))
+        d = info.as_dict()
+        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+
+    def solve_gmres(self, b, restart=30, max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
+        """A x = b by GMRES(restart) preconditioned by this (bmsp_fsai_solve_gmres): gmres_solve's arguments and results"""
+        x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
+        info = KrylovInfo()
+        check(lib().bmsp_fsai_solve_gmres(self.h, int(restart), b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
+                                          hist.ctypes.data if history else None, C.byref(info), stream))
         d = info.as_dict()
         return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
 

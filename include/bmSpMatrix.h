@@ -461,6 +461,56 @@ public:
     }
 };
 
+/* FSAI (bmsp_matrix_fsai / bmsp_fsai_*): bmSparse_fsai makes G, the factorised sparse approximate inverse of op(A) on the lower-triangular
+ * pattern of S (every row stores its diagonal, nothing to its right and at most 64 entries), scaled by BMSP_FSAI_SCALE_NONE / _SQRT /
+ * _UNIT; pivot (may be null) takes the n values y_m on the device.  bmSpFsai is the preconditioner z = G2^T (G1 r) by two sparse products:
+ * kind BMSP_FSAI_SPD (CG may use it) or BMSP_FSAI_GENERAL, flags BMSP_FSAI_NO_MATERIALISE | BMSP_FSAI_COLMAJOR.  A is borrowed and must
+ * outlive the object; S may go after construction.  apply: z != r, device pointers; solve / solve_gmres: bmSparse_solve's and
+ * bmSparse_solve_gmres's arguments; update: new factor values after a value update of A.  Synchronous like bmSparse_SpMV. */
+template <class ValueIn, class ValueS>
+inline void bmSparse_fsai(bmSpMatrix<ValueIn> &A, int op, bmSpMatrix<ValueS> &S, bmSpMatrix<ValueIn> &G, int scale = BMSP_FSAI_SCALE_SQRT,
+                          bool transposed_layout = false, typename bmsp::vector_of<ValueIn>::type *pivot = nullptr, bmsp_fsai_info *info = nullptr)
+{
+    bmsp_matrix_t g = nullptr;
+    bmsp_fsai_info local;
+    bmsp::check(bmsp_matrix_fsai(A.handle(), op, S.handle(), scale, transposed_layout ? 1 : 0, pivot, nullptr, &g, info ? info : &local));
+    G.reset(g);
+}
+template <class valueType> class bmSpFsai {
+    bmsp_fsai_t h_ = nullptr;
+
+public:
+    typedef typename bmsp::vector_of<valueType>::type vectorType;
+    template <class ValueS>
+    bmSpFsai(bmSpMatrix<valueType> &A, bmSpMatrix<ValueS> &S, int kind = BMSP_FSAI_SPD, int flags = 0)
+    {
+        bmsp::check(bmsp_fsai_create(A.handle(), S.handle(), kind, flags, nullptr, &h_));
+    }
+    bmSpFsai(const bmSpFsai &) = delete;
+    bmSpFsai &operator=(const bmSpFsai &) = delete;
+    ~bmSpFsai() { if (h_) bmsp_fsai_free(h_); }
+    bmsp_fsai_t handle() const { return h_; }
+    void info(bmsp_fsai_handle_info *out) const { bmsp::check(bmsp_fsai_get_info(h_, out)); }
+    void update() { bmsp::check(bmsp_fsai_update(h_, nullptr)); }
+    void apply(const vectorType *r, vectorType *z)
+    {
+        bmsp::check(bmsp_fsai_apply(h_, r, z, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+    void solve(int method, const vectorType *b, vectorType *x, int64_t max_iter = 0, double tol = 1e-6, int flags = 0,
+               double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
+    {
+        bmsp::check(bmsp_fsai_solve(h_, method, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+    void solve_gmres(int restart, const vectorType *b, vectorType *x, int64_t max_iter = 0, double tol = 1e-6, int flags = 0,
+                     double *relres_history = nullptr, bmsp_krylov_info *info = nullptr)
+    {
+        bmsp::check(bmsp_fsai_solve_gmres(h_, restart, b, x, max_iter, tol, flags, relres_history, info, nullptr));
+        bmsp::check(bmsp_synchronize());
+    }
+};
+
 /* Block multi-colour ordering and block permutation (bmsp_matrix_color_blocks / bmsp_matrix_permute_blocks / bmsp_vec_permute_blocks).
  * bmSparse_color_blocks: the greedy colouring of the block-row graph of a square A by hashed priorities into colors and the ordering by
  * colour class into perm (new -> old), both resized to ceil(num_rows / 8); the triangles of bmSparse_permute_blocks(A, perm, perm, B)

@@ -954,6 +954,88 @@ int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t 
 int bmsp_mg_solve_gmres(bmsp_mg_t mg, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
                         double *relres_history, bmsp_krylov_info *info, void *stream);
 
+/* FSAI on the device: the factorised sparse approximate inverse (Kolotilina-Yeremin) on a prescribed lower-triangular pattern, the
+ * preconditioner that is applied by sparse products alone, z = G^T (G r): no levels, no sweeps, nothing that can fail to contract.
+ * Nothing in the reference is replaced (it has no solver).
+ *   bmsp_matrix_fsai: *out = G, a new matrix with S's structure -- copied as bmsp_sddmm copies S's: no sort, scan, atomic or COO round
+ *       trip -- A's dtype and its tiles in layout out_transposed.  A is square, n x n, F32 or F64 (F16: BMSP_ERR_UNSUPPORTED, as in
+ *       bmsp_krylov_solve), in either tile layout.  S gives the pattern only (values and dtype ignored), n x n, either layout; every row
+ *       i of S stores the diagonal and nothing to its right.  d_pivot (may be NULL) takes n elements of the vector type R (float for F32,
+ *       double for F64).  A and S are never modified.  n == 0 is legal.  The call synchronises `stream` (the pattern check, bad_rows).
+ *   bmsp_matrix_fsai_values: refills a G made by the first call -- or any matrix of A's shape and dtype with a legal pattern, never A
+ *       itself -- after A's values changed, and drops G's value-derived caches as bmsp_matrix_copy_values does.  It synchronises `stream`
+ *       too: G's pattern is checked on every call (the handle keeps no record of it), and bad_rows is read back.
+ *   Arithmetic, fixed operation by operation, row by row (tests/fsai_ref.c restates it).  Nothing is contracted except the named fma.
+ *       1. P = (p_1 < .. < p_m = i) are the stored columns of row i of S.
+ *       2. B is m x m in R: B_ab is the stored entry of op(A) at (p_a, p_b), or +0 if none is stored.
+ *       3. LU without pivoting: for k = 1 .. m-1, with pivot B_kk, for a = k+1 .. m: L_ak = B_ak / B_kk (one IEEE division), then for
+ *          b = k+1 .. m: B_ab = fma(-L_ak, B_kb, B_ab).
+ *       4. y_m = 1 / B_mm.
+ *       5. For a = m-1 down to 1: s = +0; for c = a+1 .. m ascending s = fma(-L_ca, y_c, s); y_a = s.  This is y^T B = e_m^T.
+ *       6. BMSP_FSAI_SCALE_NONE: g = y.  BMSP_FSAI_SCALE_SQRT: q = sqrt(y_m), g_a = y_a / q for every a.  BMSP_FSAI_SCALE_UNIT:
+ *          g_a = y_a / y_m for every a.
+ *       7. G[i, p_a] = g_a, d_pivot[i] = y_m.
+ *       Every B_ab is one chain in k order and every y_a one chain in c order, so the bits do not depend on how a row is computed: W
+ *       lanes per row, W the smallest of 8, 16, 32, 64 that holds the longest row of S (a pure function of S's structure), a lane per
+ *       row of B, B in LDS sized from W alone.  BMSP_FSAI_LANES=<W> (read per call) forces a larger W and never changes the bits.  No
+ *       flag, no spin, no floating-point atomic: only the integer count of bad rows.  op T runs on a temporary bmsp_matrix_transpose(A),
+ *       freed before the call returns.
+ *   Breakdown: a zero or non-finite pivot, or a negative y_m under SQRT, is not refused: IEEE gives Inf / NaN in that row and only in
+ *       that row (BMSP_PC_JACOBI's rule).  info->bad_rows counts the rows of G that hold a non-finite value.
+ *   bmsp_fsai_info: the kernel instantiation by name, W (lanes), rows, the longest row, the sum of m^2 over the rows (pairs), bad_rows
+ *       and the LDS bytes per workgroup.
+ *   BMSP_ERR_LIMIT: the first row of S with more than 64 stored entries, the message naming the row and its length (thin the pattern
+ *       first, bmsp_matrix_prune); 2^32 tiles or values or more.
+ *   BMSP_ERR_INVALID, the message naming the argument, scalars before handles, nothing left allocated: op, scale or out_transposed out
+ *       of range; a null A, S, G, out or info; a non-square A; shapes that differ; row-panel views; the first row of S whose diagonal is
+ *       not stored; the first row of S that stores a column to the right of the diagonal.  *out is untouched by a refused call. */
+#define BMSP_FSAI_SCALE_NONE 0
+#define BMSP_FSAI_SCALE_SQRT 1
+#define BMSP_FSAI_SCALE_UNIT 2
+typedef struct { char kernel[64]; int lanes; int64_t rows, max_row, pairs, bad_rows, lds_bytes; } bmsp_fsai_info;
+int bmsp_matrix_fsai(bmsp_matrix_t A, int op, bmsp_matrix_t S, int scale, int out_transposed, void *d_pivot /* n of R, may be NULL */,
+                     void *stream, bmsp_matrix_t *out, bmsp_fsai_info *info);
+int bmsp_matrix_fsai_values(bmsp_matrix_t A, int op, bmsp_matrix_t G, int scale, void *d_pivot, void *stream, bmsp_fsai_info *info);
+
+/* The FSAI preconditioner handle.  bmsp_precond is fixed and kind 4 stays refused: like bmsp_mg_t this has its own handle and its own
+ * solves, bound to the preconditioner hook of bmsp_krylov_solve / bmsp_gmres_solve.
+ *   Kinds: BMSP_FSAI_SPD: G = fsai(A, N, S, SQRT) and z = G^T (G r); G A G^T has a unit diagonal and the preconditioner is symmetric
+ *       positive definite, so CG may use it.  BMSP_FSAI_GENERAL: L^ = fsai(A, N, S, NONE), W = fsai(A, T, S, UNIT), z = W^T (L^ r); with
+ *       full patterns this is U^-1 D^-1 L^-1 exactly, and for a symmetric A it equals the SPD kind in exact arithmetic.
+ *   Application: exactly two public products, and its bits are theirs: t = bmsp_spmv_op(G1, N, 1, r, 0, t), then by default z =
+ *       bmsp_spmv_op(G2t, N, 1, t, 0, z) on a transpose the handle materialises with bmsp_matrix_transpose, or under
+ *       BMSP_FSAI_NO_MATERIALISE z = bmsp_spmv_op(G2, T, 1, t, 0, z).  BMSP_FSAI_COLMAJOR puts every factor (and transpose) in the
+ *       column-major layout, bmsp_spmv_op's pure view case.  (SPD: G1 = G2 = G.  GENERAL: G1 = L^, G2 = W.)
+ *   The handle borrows A and owns its factors, its transpose and one work vector; S may be freed after create.  bmsp_fsai_create and
+ *       bmsp_fsai_update (new factor values after a value update of A) synchronise `stream`.  bmsp_fsai_factors lends the two factor
+ *       handles (either pointer may be NULL).  bmsp_fsai_apply (d_z must not be d_r) is asynchronous: the views the products
+ *       need are built at create.  One stream per handle at a time.  bmsp_fsai_free does not synchronise.  bmsp_fsai_get_info reports the
+ *       kind, the flags, n, whether the transpose is materialised, the bmsp_fsai_info of both factors and the bytes the handle owns.
+ *   bmsp_fsai_solve / bmsp_fsai_solve_gmres: bmsp_krylov_solve(A, BMSP_OP_N, method, ...) / bmsp_gmres_solve(A, BMSP_OP_N, ., restart,
+ *       ...) with that application as z = M^-1 r: their arithmetic, stop and breakdown rules, modes, history, info and refusals.
+ *       info->method is "cg+fsai", "bicgstab+fsai" or "gmres(<m>)+fsai"; precond_applies counts applications.  The views are built
+ *       before the first iteration is enqueued.  As with the ILU kinds, the two library products of an iteration enqueued behind a stop
+ *       still run on work vectors: the only wasted work.  bad_rows > 0 is not refused: the solve ends in BMSP_KRYLOV_BREAKDOWN.  n == 0
+ *       returns BMSP_KRYLOV_CONVERGED after 0 iterations.
+ *   Refused with BMSP_ERR_INVALID: an unknown kind; flags with unknown bits; a null A, S, out, handle or vector; what bmsp_matrix_fsai
+ *       refuses; for the solves what bmsp_krylov_solve / bmsp_gmres_solve refuse. */
+#define BMSP_FSAI_SPD 0
+#define BMSP_FSAI_GENERAL 1
+#define BMSP_FSAI_NO_MATERIALISE 1
+#define BMSP_FSAI_COLMAJOR 2
+typedef struct bmsp_fsai_s *bmsp_fsai_t;
+typedef struct { int kind, flags, materialised; int64_t n, owned_bytes; bmsp_fsai_info factor[2]; } bmsp_fsai_handle_info;
+int bmsp_fsai_create(bmsp_matrix_t A, bmsp_matrix_t S, int kind, int flags, void *stream, bmsp_fsai_t *out);
+int bmsp_fsai_update(bmsp_fsai_t f, void *stream);
+int bmsp_fsai_free(bmsp_fsai_t f);
+int bmsp_fsai_get_info(bmsp_fsai_t f, bmsp_fsai_handle_info *info);
+int bmsp_fsai_factors(bmsp_fsai_t f, bmsp_matrix_t *G1, bmsp_matrix_t *G2);
+int bmsp_fsai_apply(bmsp_fsai_t f, const void *d_r, void *d_z, void *stream);
+int bmsp_fsai_solve(bmsp_fsai_t f, int method, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                    double *relres_history, bmsp_krylov_info *info, void *stream);
+int bmsp_fsai_solve_gmres(bmsp_fsai_t f, int restart, const void *d_b, void *d_x, int64_t max_iter, double tol, int flags,
+                          double *relres_history, bmsp_krylov_info *info, void *stream);
+
 /* SDDMM, the sampled dense-dense product on the pattern of S: for every stored coordinate (i, j) of S
  *       c_ij = alpha * d_ij + beta * s_ij      or, under BMSP_SDDMM_MUL_S,      c_ij = alpha * d_ij * s_ij,      d_ij = sum_{t<k} X[i][t] * Y[j][t]
  * on the device, without a COO round trip (the gradient of bmsp_spmm with respect to A's values, the edge scores of graph attention, the

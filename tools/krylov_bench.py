@@ -22,6 +22,12 @@ one and of two full cycles).  --ortho times the orthogonalisation: one iteration
 (t(j + 1 iterations) - t(j iterations) under NO_CHECK, the median of 8 * reps + 1 back-to-back pairs: the product of one entry per row, two passes of dots and updates, the scalar
 kernel, the normalisation) under BMSP_GMRES_GROUP in {4, 8, 16}, against the same two passes assembled from public calls -- j + 1
 bmsp_vec_dot and j + 1 bmsp_vec_axpby each -- for j in {7, 15, 29} and n in {2^18, 2^21}, fp32.
+--fsai times the FSAI preconditioner (bmsp_fsai_*), fp32, on the five matrices: the pattern is tril(A), thinned by fsai_pattern(A, theta)
+with the smallest theta of 0, 0.02, 0.05, 0.1, 0.2, 0.4 at which no row exceeds 64 entries; per matrix theta, the longest row, W, the set-up
+(pattern_ms, create_ms: factors, transposes and views; wall clock), one application against two bmsp_spmv_op on tril(A) and against
+Jacobi's (the difference of a NO_CHECK iteration with jacobi and with none), and CG (symmetric matrices, SPD kind) / BiCGStab / GMRES(30)
+(GENERAL kind) against none and jacobi: iterations, call_us, time to solution with and without set-up.  lanes_us: bmsp_matrix_fsai_values
+under BMSP_FSAI_LANES in {default, 16, 32, 64}.
 Prints one JSON line."""
 import argparse
 import json
@@ -218,6 +224,74 @@ def bench_gmres(name, n, r, c, v, dtype, a):
     return row
 
 
+def bench_fsai(name, method, n, r, c, v, a):
+    R = np.float32
+    A = B.BmSpMatrix.from_coo(n, n, r, c, v, dtype=B.F32)
+    row = {"matrix": name, "dtype": "fp32", "rows": n, "nnz": A.info()["nnz"]}
+    hb = np.random.default_rng(7).uniform(-1.0, 1.0, n).astype(R)
+    b, x, z = B.DeviceArray.from_host(hb), B.DeviceArray(n, R), B.DeviceArray(n, R)
+    symmetric = method == "cg"
+    kind = "spd" if symmetric else "general"
+    S = f = None
+    for theta in (0.0, 0.02, 0.05, 0.1, 0.2, 0.4):
+        S, row["pattern_ms"] = wall_ms(lambda: B.fsai_pattern(A, theta))
+        try:
+            f, row["create_ms"] = wall_ms(lambda: B.Fsai(A, S, kind))
+        except B.BmspError as e:
+            if e.status != -6:
+                raise
+            continue
+        row["theta"] = theta
+        break
+    if f is None:
+        row["error"] = "no theta up to 0.4 leaves rows of at most 64 entries"
+        return row
+    fi = f.info()["factor"][0]
+    row.update({"pattern_nnz": S.info()["nnz"], "max_row": fi["max_row"], "lanes": fi["lanes"], "kernel": fi["kernel"], "bad_rows": fi["bad_rows"],
+                "setup_ms": round(row["pattern_ms"] + row["create_ms"], 3)})
+    G = B.fsai(A, S, "N", "sqrt")[0]
+    row["lanes_us"] = {}
+    for lanes in (None, "16", "32", "64"):
+        if lanes is None:
+            os.environ.pop("BMSP_FSAI_LANES", None)
+        else:
+            os.environ["BMSP_FSAI_LANES"] = lanes
+        row["lanes_us"]["default" if lanes is None else lanes] = event_us(lambda: B.fsai_values(A, G, "N", "sqrt"), a.reps, 2)
+    os.environ.pop("BMSP_FSAI_LANES", None)
+    row["apply_us"] = event_us(lambda: f.apply(b, z), a.reps, 3)
+    view = B.Fsai(A, S, kind, materialise=False)
+    row["apply_no_materialise_us"] = event_us(lambda: view.apply(b, z), a.reps, 3)
+    del view
+    row["two_spmv_tril_us"] = event_us(lambda: (B.spmv_op(S, b, "N", u=z), B.spmv_op(S, z, "N", u=x)), a.reps, 3)
+    row["spmv_us"] = event_us(lambda: B.spmv_op(A, b, "N", u=z), a.reps, 3)
+    set_check(None)
+    methods = (["cg"] if symmetric else []) + ["bicgstab", "gmres"]
+    row["solve"] = {}
+    handles = {"spd": f} if symmetric else {"general": f}
+    if symmetric:
+        handles["general"], row["create_general_ms"] = wall_ms(lambda: B.Fsai(A, S, "general"))
+    for m in methods:
+        per = {}
+        h = handles["spd" if m == "cg" else "general"]
+        setup = row["pattern_ms"] + (row["create_general_ms"] if symmetric and m != "cg" else row["create_ms"])
+        runs = {"none": lambda **kw: (B.gmres_solve(A, b, None, restart=a.restart, x=x, **kw) if m == "gmres" else B.krylov_solve(A, b, m, None, x=x, **kw)),
+                "jacobi": lambda **kw: (B.gmres_solve(A, b, "jacobi", restart=a.restart, x=x, **kw) if m == "gmres" else B.krylov_solve(A, b, m, "jacobi", x=x, **kw)),
+                "fsai": lambda **kw: (h.solve_gmres(b, a.restart, x=x, **kw) if m == "gmres" else h.solve(b, m, x=x, **kw))}
+        for label, run in runs.items():
+            (_, info), first_ms = wall_ms(lambda: run(max_iter=a.cap, tol=TOL))
+            q = {"iterations": info["iterations"], "status": info["status"], "relres": info["relres"]}
+            q["call_us"] = event_us(lambda: run(max_iter=a.cap, tol=TOL), a.reps)
+            steps = a.restart if m == "gmres" else 16
+            t1 = event_us(lambda: run(max_iter=steps, tol=B.KRYLOV_NO_CHECK), a.reps)
+            t2 = event_us(lambda: run(max_iter=2 * steps, tol=B.KRYLOV_NO_CHECK), a.reps)
+            q["iter_us"] = round((t2 - t1) / steps, 2)
+            q["time_to_solution_ms"] = round((setup if label == "fsai" else 0.0) + q["call_us"] / 1e3, 3)
+            per[label] = q
+        per["jacobi_apply_us"] = round((per["jacobi"]["iter_us"] - per["none"]["iter_us"]) / (2 if m == "bicgstab" else 1), 2)
+        row["solve"][m] = per
+    return row
+
+
 def paired_us(short, long, pairs):
     """median over `pairs` of t(long) - t(short), the two timed back to back with HIP events"""
     e = [B.Event() for _ in range(3)]
@@ -267,6 +341,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gmres", action="store_true", help="GMRES(--restart) against BiCGStab, time to solution")
     ap.add_argument("--ortho", action="store_true", help="the orthogonalisation step against public calls")
+    ap.add_argument("--fsai", action="store_true", help="the FSAI preconditioner against none and jacobi, fp32")
     ap.add_argument("--restart", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cap", type=int, default=2000)
@@ -300,6 +375,10 @@ def main():
         n, _, r, c, v = make()
         if dominant:
             r, c, v = with_dominant_diagonal(n, r, c, v)
+        if a.fsai:
+            rows.append(bench_fsai(name, method, n, r, c, v, a))
+            print("row " + json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            continue
         for dt in a.dtypes.split(","):
             if a.gmres:
                 rows.append(bench_gmres(name, n, r, c, v, B.F64 if dt == "fp64" else B.F32, a))
