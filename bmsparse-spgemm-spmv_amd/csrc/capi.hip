@@ -64,6 +64,13 @@ static void need(const void *p, const char *what)
     if (!p) fail(BMSP_ERR_INVALID, "%s is null", what);
 }
 
+// what every solve entry refuses about its handle and its vectors, between the argument checks and the operand checks
+static void need_solve_operands(const void *handle, const char *what, const void *d_b, const void *d_x)
+{
+    need(handle, what); need(d_b, "d_b"); need(d_x, "d_x");
+    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+}
+
 static bmsp_matrix_s *build_from_host_coo(int num_rows, int num_cols, int64_t nnz, const int *rows, const int *cols, const double *vals,
                                           int transposed, bmsp_dtype dtype)
 {
@@ -849,10 +856,10 @@ int bmsp_krylov_solve(bmsp_matrix_t A, int op, int method, const bmsp_precond *p
 {
     BMSP_API_BEGIN
     krylov_check_args(op, method, pc, max_iter, tol, flags, relres_history);
-    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
-    krylov_check_operands(A, pc, d_b, d_x);
+    need_solve_operands(A, "matrix A", d_b, d_x);
+    krylov_check_operands(A, pc);
     load_kernels();
-    krylov_solve(A, op, method, pc, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    krylov_solve(A, op, method, SolvePc{pc}, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 
@@ -861,10 +868,10 @@ int bmsp_gmres_solve(bmsp_matrix_t A, int op, const bmsp_precond *pc, int restar
 {
     BMSP_API_BEGIN
     gmres_check_args(op, restart, pc, max_iter, tol, flags, relres_history);
-    need(A, "matrix A"); need(d_b, "d_b"); need(d_x, "d_x");
-    krylov_check_operands(A, pc, d_b, d_x);
+    need_solve_operands(A, "matrix A", d_b, d_x);
+    krylov_check_operands(A, pc);
     load_kernels();
-    gmres_solve(A, op, pc, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    gmres_solve(A, op, SolvePc{pc}, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 
@@ -915,10 +922,11 @@ int bmsp_mg_solve(bmsp_mg_t mg, int method, const void *d_b, void *d_x, int64_t 
 {
     BMSP_API_BEGIN
     krylov_check_args(BMSP_OP_N, method, nullptr, max_iter, tol, flags, relres_history);
-    need(mg, "mg"); need(d_b, "d_b"); need(d_x, "d_x");
-    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    need_solve_operands(mg, "mg", d_b, d_x);
     load_kernels();
-    mg_solve(mg, method, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    bmsp_matrix_s *A = nullptr;
+    const SolvePc pc = mg_solve_pc(mg, as_stream(stream), &A);
+    krylov_solve(A, BMSP_OP_N, method, pc, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 
@@ -927,10 +935,11 @@ int bmsp_mg_solve_gmres(bmsp_mg_t mg, int restart, const void *d_b, void *d_x, i
 {
     BMSP_API_BEGIN
     gmres_check_args(BMSP_OP_N, restart, nullptr, max_iter, tol, flags, relres_history);
-    need(mg, "mg"); need(d_b, "d_b"); need(d_x, "d_x");
-    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    need_solve_operands(mg, "mg", d_b, d_x);
     load_kernels();
-    mg_solve_gmres(mg, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    bmsp_matrix_s *A = nullptr;
+    const SolvePc pc = mg_solve_pc(mg, as_stream(stream), &A);
+    gmres_solve(A, BMSP_OP_N, pc, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 
@@ -1017,10 +1026,11 @@ int bmsp_fsai_solve(bmsp_fsai_t f, int method, const void *d_b, void *d_x, int64
 {
     BMSP_API_BEGIN
     krylov_check_args(BMSP_OP_N, method, nullptr, max_iter, tol, flags, relres_history);
-    need(f, "f"); need(d_b, "d_b"); need(d_x, "d_x");
-    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    need_solve_operands(f, "f", d_b, d_x);
     load_kernels();
-    fsai_solve(f, method, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    bmsp_matrix_s *A = nullptr;
+    const SolvePc pc = fsai_solve_pc(f, as_stream(stream), &A);
+    krylov_solve(A, BMSP_OP_N, method, pc, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 
@@ -1029,10 +1039,11 @@ int bmsp_fsai_solve_gmres(bmsp_fsai_t f, int restart, const void *d_b, void *d_x
 {
     BMSP_API_BEGIN
     gmres_check_args(BMSP_OP_N, restart, nullptr, max_iter, tol, flags, relres_history);
-    need(f, "f"); need(d_b, "d_b"); need(d_x, "d_x");
-    if (d_b == d_x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
+    need_solve_operands(f, "f", d_b, d_x);
     load_kernels();
-    fsai_solve_gmres(f, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
+    bmsp_matrix_s *A = nullptr;
+    const SolvePc pc = fsai_solve_pc(f, as_stream(stream), &A);
+    gmres_solve(A, BMSP_OP_N, pc, restart, d_b, d_x, max_iter, tol, flags, relres_history, info, as_stream(stream));
     BMSP_API_END
 }
 

@@ -1,18 +1,15 @@
-// dot_tree.hip.h -- what the solvers share (krylov.hip: bmsp_vec_dot, CG, BiCGStab; gmres.hip: GMRES(m)): the fixed two-level tree of
-// the dot product, the hand-off that lets the last workgroup finish it, and the host-side rules of a solve (chunks, the ticket
-// threshold, the check ramp, the record).  include/bmsp.h writes the tree out; tests/krylov_ref.c restates it.
+// dot_tree.hip.h -- what the solvers share on the device (krylov.hip: bmsp_vec_dot, CG, BiCGStab; gmres.hip: GMRES(m)): the fixed two-level
+// tree of the dot product, the hand-off that lets the last workgroup finish it, the stop rule and the bb / thr step of a solve, and the
+// record; with them the host-side rules of the tree (chunks, the ticket threshold).  The host side of a solve is solve_driver.hip.h.
+// include/bmsp.h writes the tree out; tests/krylov_ref.c restates it.
 #pragma once
+#include "solve_schedule.h"
 #include "sweep_stats.hip.h"
 #include <cstring>
 
 namespace bmsp {
 namespace {
 
-constexpr int64_t kMaxIter = 1ll << 20;
-// Iterations enqueued between two read-backs when BMSP_KRYLOV_CHECK does not say: 1, 2, 4, 8, then 16 per batch.  What is enqueued behind
-// a stop is wasted products and preconditioner applications, so a solve of one or two iterations wants 1 and a long one 8 - 16 (measured
-// in DESIGN §4 "Krylov solvers"): the ramp reads back after iterations 1, 3, 7, 15, 31, 47, ...
-constexpr int64_t kCheckRampMax = 16;
 constexpr int kChunk = 4 * kThreads;  // elements per workgroup: lane t takes base + 256 q + t, q = 0..3
 // The second level of a dot runs in the last arriver up to this many chunks and as a launch of its own beyond: the tickets are
 // same-address atomics and serialise at the memory side, about 11 ns each.  Measured, us per dot, ticket / launch: 64 chunks 5.5 / 8.6,
@@ -83,6 +80,50 @@ __device__ __forceinline__ double dot_term(R x, R y, double acc)
 }
 
 __device__ __forceinline__ bool bad_denominator(double v) { return v == 0.0 || !__builtin_isfinite(v); }
+
+// ---- the scalars of a solve: State is KrylovState or GmresState, whose kernels read `stopped` first ----
+template <typename State>
+__device__ __forceinline__ void stop(State *S, int status)
+{
+    S->status = status;
+    S->stopped = 1;
+}
+
+// The stop rule on a residual dot, three ways; before_breakdown() runs first on the two breakdown branches.  True if the solve goes on.
+// (rr == 0 above thr: NO_CHECK, thr < 0)
+struct NothingBefore {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <typename State, typename Before = NothingBefore>
+__device__ __forceinline__ bool residual_verdict(State *S, double rr, Before before_breakdown = Before())
+{
+    if (!__builtin_isfinite(rr)) {
+        before_breakdown();
+        stop(S, BMSP_KRYLOV_BREAKDOWN);
+    } else if (rr <= S->thr) {
+        stop(S, BMSP_KRYLOV_CONVERGED);
+    } else if (rr == 0.0) {
+        before_breakdown();
+        stop(S, BMSP_KRYLOV_BREAKDOWN);
+    } else {
+        return true;
+    }
+    return false;
+}
+
+// bb = dot(b, b) has been formed: thr = fl(tol2 * bb), or -1 under NO_CHECK (tol2 < 0); the zero and the non-finite stops, in that order;
+// go_on() where neither fell.
+template <typename State, typename GoOn>
+__device__ __forceinline__ void bb_step(State *S, double bb, double tol2, GoOn go_on)
+{
+#pragma clang fp contract(off)
+    S->bb = bb;
+    const double thr = tol2 * bb;
+    S->thr = tol2 < 0.0 ? -1.0 : thr;
+    if (bb == 0.0) return stop(S, BMSP_KRYLOV_CONVERGED);
+    if (!__builtin_isfinite(bb)) return stop(S, BMSP_KRYLOV_BREAKDOWN);
+    go_on();
+}
 
 // whether the last arriver finishes a dot of `chunks` chunks (else a launch of its own does)
 bool finish_by_ticket(int64_t chunks)

@@ -477,20 +477,15 @@ void fsai_apply(bmsp_fsai_s *f, const void *r, void *z, hipStream_t st)
     else spmv_op(f->G2(), BMSP_OP_T, 1.0, f->work, 0.0, z, st);
 }
 
-void fsai_solve(bmsp_fsai_s *f, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                bmsp_krylov_info *info, hipStream_t st)
+SolvePc fsai_solve_pc(bmsp_fsai_s *f, hipStream_t st, bmsp_matrix_s **A)
 {
     build_views(f, st);  // (made at create; a bmsp_matrix_invalidate on a lent factor since then has dropped them)
-    const KrylovHook hook = [f](const void *in, void *out, const int *, hipStream_t s) { fsai_apply(f, in, out, s); };
-    krylov_solve_hooked(f->A, method, hook, "fsai", b, x, max_iter, tol, flags, relres_history, info, st);
-}
-
-void fsai_solve_gmres(bmsp_fsai_s *f, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                      bmsp_krylov_info *info, hipStream_t st)
-{
-    build_views(f, st);
-    const KrylovHook hook = [f](const void *in, void *out, const int *, hipStream_t s) { fsai_apply(f, in, out, s); };
-    gmres_solve_hooked(f->A, restart, hook, "fsai", b, x, max_iter, tol, flags, relres_history, info, st);
+    *A = f->A;
+    SolvePc pc;
+    pc.hook = [](void *h, const void *in, void *out, const int *, hipStream_t s) { fsai_apply((bmsp_fsai_s *)h, in, out, s); };
+    pc.handle = f;
+    pc.name = "fsai";
+    return pc;
 }
 
 }  // namespace bmsp

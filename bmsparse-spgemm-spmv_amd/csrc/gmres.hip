@@ -10,12 +10,12 @@
 //   gmres_scalar_kernel  one workgroup: the second level of dot(w, w), then in thread 0 the column of the Hessenberg matrix, the Givens
 //       rotations, the record and the stop rule.
 //   gmres_scale_kernel (the normalisation), gmres_y_kernel (the back substitution, one thread) and gmres_xform_kernel (x += Z y).
+// The host side is krylov.hip's too (solve_driver.hip.h): run_gmres keeps the workspace layout, GmresArgs, the launches of one iteration
+// and the x-formation after a stop inside a cycle.
 // Termination is krylov.hip's protocol: every kernel reads `stopped` first and returns without writing once it is set.  The exception
 // is the pair that forms x: the scalar kernel leaves in `J` the columns the cycle has completed (0 after a breakdown), gmres_y_kernel
 // takes them over and clears J, so the x-formation enqueued behind a stop still applies the cycle the stop fell into, exactly once.
-#include "dot_tree.hip.h"
-#include <cmath>
-#include <vector>
+#include "solve_driver.hip.h"
 
 namespace bmsp {
 namespace {
@@ -23,7 +23,6 @@ namespace {
 constexpr int kDefaultRestart = 30, kMaxRestart = 256;
 // Basis vectors per launch of gmres_dots_kernel; BMSP_GMRES_GROUP=1..16 (read per call) sets another.  The bits do not depend on it.
 constexpr int kMaxGroup = 16, kDefaultGroup = 8;
-constexpr int kPcHook = BMSP_PC_ILU_SWEEPS + 1;  // (krylov.hip's: the preconditioner is a callable)
 
 // The scalars of one solve, device-resident.  `stopped` is what every kernel reads first; `status` is a BMSP_KRYLOV_* value.
 struct GmresState {
@@ -53,21 +52,13 @@ struct GmresArgs {
     double tol2;        // fl(tol * tol), or negative under NO_CHECK
 };
 
-__device__ __forceinline__ void stop(GmresState *S, int status)
-{
-    S->status = status;
-    S->stopped = 1;
-}
-
 // The residual dot at the start of a cycle: the stop rule, then beta, g_0 and the scale of v_0.
 template <typename R>
 __device__ __forceinline__ void begin_cycle(const GmresArgs<R> &a, double rr)
 {
     GmresState *S = a.S;
     S->rr = rr;
-    if (!__builtin_isfinite(rr)) return stop(S, BMSP_KRYLOV_BREAKDOWN);
-    if (rr <= S->thr) return stop(S, BMSP_KRYLOV_CONVERGED);
-    if (rr == 0.0) return stop(S, BMSP_KRYLOV_BREAKDOWN);  // (NO_CHECK: thr < 0)
+    if (!residual_verdict(S, rr)) return;
     const double beta = __builtin_sqrt(rr);
     S->scale = 1.0 / beta;
     a.g[0] = beta;
@@ -110,12 +101,9 @@ __global__ __launch_bounds__(kThreads) void gmres_start_finish_kernel(GmresArgs<
     const double s = finish_sum(a.P, a.chunks, lds4);
     if (threadIdx.x != 0) return;
     if (STEP == kStartBB) {
-        S->bb = s;
-        const double thr = a.tol2 * s;
-        S->thr = a.tol2 < 0.0 ? -1.0 : thr;
-        if (s == 0.0) return stop(S, BMSP_KRYLOV_CONVERGED);
-        if (!__builtin_isfinite(s)) return stop(S, BMSP_KRYLOV_BREAKDOWN);
-        if (!a.x0) begin_cycle(a, s);  // (r = b)
+        bb_step(S, s, a.tol2, [&]() {
+            if (!a.x0) begin_cycle(a, s);  // (r = b)
+        });
     } else {
         S->products++;
         begin_cycle(a, s);
@@ -331,15 +319,7 @@ __global__ __launch_bounds__(kThreads) void gmres_scalar_kernel(GmresArgs<R> a, 
         a.rec[k - 1].rr = rr;
         a.rec[k - 1].written = 1;
     }
-    if (!__builtin_isfinite(rr)) {
-        S->J = 0;
-        stop(S, BMSP_KRYLOV_BREAKDOWN);
-    } else if (rr <= S->thr) {
-        stop(S, BMSP_KRYLOV_CONVERGED);
-    } else if (rr == 0.0) {  // (NO_CHECK: thr < 0)
-        S->J = 0;
-        stop(S, BMSP_KRYLOV_BREAKDOWN);
-    }
+    residual_verdict(S, rr, [S]() { S->J = 0; });
 }
 
 // The back substitution for the J columns the cycle completed, in thread 0; takes J over (Jx) and clears it.  Runs after a stop too.
@@ -420,14 +400,13 @@ void launch_dots(const GmresArgs<R> &a, int j, int first, int count, double *t, 
 }
 
 template <typename R>
-void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHook *hook, const char *hook_name, int restart, const void *b,
-               void *x, int64_t max_it, double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+void run_gmres(const SolveCall &c, int restart)
 {
-    const int64_t n = A->num_rows;
-    const int kind = hook ? kPcHook : (pc ? pc->kind : BMSP_PC_NONE);
-    const bool checked = !no_check(tol), x0 = (flags & BMSP_KRYLOV_X0_GIVEN) != 0;
-    const bool ilu = kind == BMSP_PC_ILU_EXACT || kind == BMSP_PC_ILU_SWEEPS;
-    bmsp_matrix_s *F = ilu ? pc->F : nullptr;
+    bmsp_matrix_s *A = c.A;
+    const hipStream_t st = c.st;
+    const int64_t n = A->num_rows, max_it = c.cap;
+    const int kind = c.kind();
+    const bool checked = c.checked();
     const int m = (int)(restart < max_it ? restart : max_it);  // (a basis beyond the cap would never be filled)
     const int group = group_from_env();
     const int64_t chunks = chunks_of(n);
@@ -437,15 +416,7 @@ void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHoo
     const size_t off_P = round256(sizeof(GmresState)), off_small = off_P + round256(sizeof(double) * kMaxGroup * (size_t)chunks);
     const size_t off_d = off_small + round256(small), off_tmp = off_d + vbytes, off_V = off_tmp + vbytes;
     const size_t off_Z = off_V + vbytes * ((size_t)m + 1), off_rec = off_Z + (kind == BMSP_PC_NONE ? 0 : vbytes * (size_t)m);
-    const size_t need = off_rec + (checked ? sizeof(KrylovRecord) * (size_t)max_it : 0);
-    if (need > A->krylov_ws_bytes) {
-        if (A->krylov_ws) BMSP_HIP(hipStreamSynchronize(st));  // (work enqueued on the old one has finished before it goes back to the pool)
-        A->krylov_ws.release();
-        A->krylov_ws_bytes = 0;
-        A->krylov_ws.alloc(need);
-        A->krylov_ws_bytes = need;
-    }
-    char *ws = (char *)A->krylov_ws;
+    char *ws = grow_workspace(A, off_rec + (checked ? sizeof(KrylovRecord) * (size_t)max_it : 0), st);  // (records: by the cap, not the restart)
     GmresArgs<R> a{};
     a.S = (GmresState *)ws;
     a.rec = checked ? (KrylovRecord *)(ws + off_rec) : nullptr;
@@ -456,43 +427,27 @@ void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHoo
     a.g = a.sn + m;
     a.y = a.g + (m + 1);
     a.t = a.y + m;
-    a.b = (const R *)b;
+    a.b = (const R *)c.b;
     a.d = (const R *)(ws + off_d);
-    a.x = (R *)x;
+    a.x = (R *)c.x;
     a.V = (R *)(ws + off_V);
     a.Z = kind == BMSP_PC_NONE ? a.V : (R *)(ws + off_Z);
     R *tmp = (R *)(ws + off_tmp);
-    a.n = n; a.stride = (int64_t)(vbytes / sizeof(R)); a.chunks = (uint32_t)chunks; a.m = m; a.pc = kind; a.x0 = x0 ? 1 : 0;
-    a.tol2 = checked ? tol * tol : -1.0;
+    a.n = n; a.stride = (int64_t)(vbytes / sizeof(R)); a.chunks = (uint32_t)chunks; a.m = m; a.pc = kind; a.x0 = c.x0() ? 1 : 0;
+    a.tol2 = c.tol2();
     const bool ticket = finish_by_ticket(chunks);
-    if (info) {
-        memset(info, 0, sizeof *info);
-        static const char *const names[4] = {"none", "jacobi", "ilu", "ilu_sweeps"};
-        snprintf(info->method, sizeof info->method, "gmres(%d)+%s", restart, hook ? hook_name : names[kind]);
-        info->max_iterations = max_it;
-        info->workspace_bytes = (int64_t)A->krylov_ws_bytes;
-    }
+    char method[24];
+    snprintf(method, sizeof method, "gmres(%d)", restart);  // (the restart asked for, not min(restart, cap))
+    begin_info(c, method);
     const dim3 cgrid((uint32_t)chunks), egrid((uint32_t)((n + kThreads - 1) / kThreads)), block(kThreads);
     const auto vec = [&](R *base, int i) { return base + (int64_t)i * a.stride; };
-    const auto product = [&](const R *in, R *out) { spmv_op(A, op, 1.0, in, 0.0, out, st); };
-    // z_j = M^-1 v_j.  The ILU kinds through tmp: L then U; under op T the transposed factors, U^T then L^T.  A hooked solve: the hook,
-    // which gets the status word every kernel of the solver reads first.
+    // z_j = M^-1 v_j
     const auto apply = [&](int j) {
-        if (kind == BMSP_PC_NONE) return;
         if (kind == BMSP_PC_JACOBI) {
             hipLaunchKernelGGL(gmres_jacobi_kernel<R>, egrid, block, 0, st, a, j);
             BMSP_CHECK_LAUNCH();
-            return;
-        }
-        if (hook) return (*hook)(vec(a.V, j), vec(a.Z, j), &a.S->stopped, st);
-        const int first = op == BMSP_OP_T ? BMSP_FILL_UPPER : BMSP_FILL_LOWER;
-        for (int half = 0; half < 2; half++) {
-            const int fill = half == 0 ? first : 1 - first;
-            const int diag = fill == BMSP_FILL_LOWER ? BMSP_DIAG_UNIT : BMSP_DIAG_NON_UNIT;
-            const R *src = half == 0 ? vec(a.V, j) : tmp;
-            R *dst = half == 0 ? tmp : vec(a.Z, j);
-            if (kind == BMSP_PC_ILU_EXACT) spsv(F, op, fill, diag, 1.0, src, dst, st);
-            else spitsv(F, op, fill, diag, 1.0, src, dst, pc->sweeps, BMSP_ITSV_NO_CHECK, 0, nullptr, nullptr, st);
+        } else if (kind != BMSP_PC_NONE) {
+            pc_apply(c, vec(a.V, j), tmp, vec(a.Z, j), &a.S->stopped);
         }
     };
     const auto scale = [&](int slot) {
@@ -501,7 +456,7 @@ void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHoo
     };
     // r = b - op(A) x into slot 0, rr, the stop rule, beta
     const auto residual = [&]() {
-        product(a.x, vec(a.V, 1));
+        product(c, a.x, vec(a.V, 1));
         hipLaunchKernelGGL((gmres_start_kernel<R, kStartR0>), cgrid, block, 0, st, a);
         BMSP_CHECK_LAUNCH();
         hipLaunchKernelGGL((gmres_start_finish_kernel<R, kStartR0>), dim3(1), block, 0, st, a);
@@ -515,50 +470,25 @@ void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHoo
         BMSP_CHECK_LAUNCH();
     };
     GmresState hs{};
-    const auto read_state = [&]() {
-        BMSP_HIP(hipStreamSynchronize(st));
-        copy_d2h_staged(&hs, a.S, sizeof hs);
-    };
-    const size_t xbytes = sizeof(R) * (size_t)n;
-
-    // ---- the start ----
-    BMSP_HIP(hipMemsetAsync(a.S, 0, sizeof(GmresState), st));
-    if (checked && max_it > 0) BMSP_HIP(hipMemsetAsync(a.rec, 0, sizeof(KrylovRecord) * (size_t)max_it, st));
-    hipLaunchKernelGGL((gmres_start_kernel<R, kStartBB>), cgrid, block, 0, st, a);
-    BMSP_CHECK_LAUNCH();
-    hipLaunchKernelGGL((gmres_start_finish_kernel<R, kStartBB>), dim3(1), block, 0, st, a);
-    BMSP_CHECK_LAUNCH();
-    bool finished = false;
-    if (checked) {
-        read_state();
-        finished = hs.stopped != 0;
-        if (finished && (hs.bb == 0.0 || !x0)) BMSP_HIP(hipMemsetAsync(x, 0, xbytes, st));
-    }
+    bool finished = solve_start(
+        c, a.S, a.rec, a.d, a.V, hs,
+        [&]() {
+            hipLaunchKernelGGL((gmres_start_kernel<R, kStartBB>), cgrid, block, 0, st, a);
+            BMSP_CHECK_LAUNCH();
+            hipLaunchKernelGGL((gmres_start_finish_kernel<R, kStartBB>), dim3(1), block, 0, st, a);
+            BMSP_CHECK_LAUNCH();
+        },
+        [&]() {
+            hipLaunchKernelGGL(gmres_zero_x_kernel<R>, egrid, block, 0, st, a);
+            BMSP_CHECK_LAUNCH();
+        },
+        residual);
     if (!finished) {
-        if (kind == BMSP_PC_JACOBI) matrix_diagonal(A, (void *)a.d, st);
-        if (x0) {
-            if (!checked) {
-                hipLaunchKernelGGL(gmres_zero_x_kernel<R>, egrid, block, 0, st, a);
-                BMSP_CHECK_LAUNCH();
-            }
-            residual();
-        } else {
-            BMSP_HIP(hipMemsetAsync(x, 0, xbytes, st));
-            BMSP_HIP(hipMemcpyAsync(a.V, b, xbytes, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    // ---- the iterations: `check` of them between two read-backs ----
-    const int64_t fixed = checked ? sweep_check_from_env("BMSP_KRYLOV_CHECK", 0) : max_it;  // (0: the ramp)
-    int64_t ramp = 1;
-    for (int64_t done = 0; done < max_it && !finished;) {
-        const int64_t check = fixed ? fixed : ramp;
-        ramp = ramp < kCheckRampMax ? 2 * ramp : kCheckRampMax;
-        const int64_t batch = check < max_it - done ? check : max_it - done;
-        for (int64_t k = done + 1; k <= done + batch; k++) {
+        finished = solve_iterations(c, a.S, hs, [&](int64_t k) {
             const int j = (int)((k - 1) % m);
             if (j == 0) scale(0);  // v_0 = fl(sR * r)
             apply(j);
-            product(vec(a.Z, j), vec(a.V, j + 1));
+            product(c, vec(a.Z, j), vec(a.V, j + 1));
             for (int pass = 0; pass < 2; pass++) {
                 double *t = a.t + pass * (m + 1);
                 for (int first = 0; first <= j; first += group)
@@ -575,53 +505,14 @@ void run_gmres(bmsp_matrix_s *A, int op, const bmsp_precond *pc, const KrylovHoo
             } else {
                 scale(j + 1);  // v_{j+1} = fl(sR * w)
             }
-        }
-        done += batch;
-        if (checked) {
-            read_state();
-            finished = hs.stopped != 0;
-        }
+        });
     }
-    if (!checked) {
-        if (info) {
-            info->iterations = max_it;
-            info->status = BMSP_KRYLOV_MAXITER;
-            info->relres = info->bnorm = -1.0;
-            info->products = max_it + (max_it > 0 ? (max_it - 1) / m : 0) + (x0 ? 1 : 0);
-            info->precond_applies = kind == BMSP_PC_NONE ? 0 : max_it;
-        }
-        return;
-    }
+    if (!checked) return no_check_info(c, max_it + (max_it > 0 ? (max_it - 1) / m : 0), max_it);
     if (finished && hs.J > 0) {  // the stop fell into a cycle whose end is not enqueued: its columns still go into x
         form_x();
         BMSP_HIP(hipStreamSynchronize(st));
     }
-    const int64_t its = hs.iterations;
-    std::vector<KrylovRecord> recs((size_t)(its > 0 ? its : 1));
-    if (its > 0) copy_d2h_staged(recs.data(), a.rec, sizeof(KrylovRecord) * (size_t)its);
-    if (relres_history)
-        for (int64_t k = 0; k < its; k++) relres_history[k] = std::sqrt(recs[(size_t)k].rr / hs.bb);
-    if (info) {
-        info->iterations = its;
-        info->status = hs.stopped ? hs.status : BMSP_KRYLOV_MAXITER;
-        info->bnorm = std::sqrt(hs.bb);
-        info->relres = hs.bb == 0.0 ? 0.0 : std::sqrt(hs.rr / hs.bb);
-        info->products = hs.products;
-        info->precond_applies = hs.applies;
-    }
-}
-
-int64_t cap_of(int64_t n, int64_t max_iter) { return max_iter ? max_iter : (n < kMaxIter ? n : kMaxIter); }
-
-bool empty_solve(int64_t n, bmsp_krylov_info *info)
-{
-    if (n != 0) return false;
-    if (info) {
-        memset(info, 0, sizeof *info);
-        snprintf(info->method, sizeof info->method, "none (empty matrix)");
-        info->status = BMSP_KRYLOV_CONVERGED;
-    }
-    return true;
+    checked_info(c, a.rec, hs);
 }
 
 }  // namespace
@@ -634,25 +525,14 @@ void gmres_check_args(int op, int restart, const bmsp_precond *pc, int64_t max_i
 }
 
 // (the arguments were checked at the C boundary: gmres_check_args, krylov_check_operands)
-void gmres_solve(bmsp_matrix_s *A, int op, const bmsp_precond *pc, int restart, const void *b, void *x, int64_t max_iter, double tol,
-                 int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+void gmres_solve(bmsp_matrix_s *A, int op, const SolvePc &pc, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags,
+                 double *relres_history, bmsp_krylov_info *info, hipStream_t st)
 {
     const int64_t n = A->num_rows;
     if (empty_solve(n, info)) return;
-    const int m = restart ? restart : kDefaultRestart;
-    if (A->dtype == BMSP_F64) run_gmres<double>(A, op, pc, nullptr, nullptr, m, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st);
-    else run_gmres<float>(A, op, pc, nullptr, nullptr, m, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st);
-}
-
-// bmsp_gmres_solve for op N with the preconditioner given as a callable (info->method: "gmres(<m>)+<name>")
-void gmres_solve_hooked(bmsp_matrix_s *A, int restart, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
-                        double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
-{
-    const int64_t n = A->num_rows;
-    if (empty_solve(n, info)) return;
-    const int m = restart ? restart : kDefaultRestart;
-    if (A->dtype == BMSP_F64) run_gmres<double>(A, BMSP_OP_N, nullptr, &hook, name, m, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st);
-    else run_gmres<float>(A, BMSP_OP_N, nullptr, &hook, name, m, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st);
+    const SolveCall c{A, op, pc, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st};
+    if (A->dtype == BMSP_F64) run_gmres<double>(c, restart ? restart : kDefaultRestart);
+    else run_gmres<float>(c, restart ? restart : kDefaultRestart);
 }
 
 }  // namespace bmsp

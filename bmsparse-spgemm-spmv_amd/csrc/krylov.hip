@@ -10,21 +10,17 @@
 //       and -- in the last arriver's thread 0 -- the scalar step: alpha, beta, omega by one IEEE division each, the stop rule, the
 //       breakdown tests, the record.  A launch per step; the scalars never leave the device.
 //   termination on the device   every instantiation begins by reading `stopped` and returns without writing once it is set.  The host
-//       enqueues BMSP_KRYLOV_CHECK iterations, reads state and records back and goes on or stops; what it enqueued behind a stop did
-//       nothing to x.
-#include "dot_tree.hip.h"
-#include <cmath>
+//       enqueues BMSP_KRYLOV_CHECK iterations, reads the state back and goes on or stops; what it enqueued behind a stop did nothing
+//       to x.
+//   the host side   solve_driver.hip.h, shared with gmres.hip: the preconditioner, the workspace, the start, the batches, the info.
+//       run_solve keeps the workspace layout, StepArgs, the start tail (r^ = r, or the first z and p) and the launches of one iteration.
+#include "solve_driver.hip.h"
 #include <map>
 #include <mutex>
 #include <utility>
 
 namespace bmsp {
 namespace {
-
-// The preconditioner kind of a hooked solve (krylov_solve_hooked: bmsp_mg_solve's cycle), internal: the public kinds end at
-// BMSP_PC_ILU_SWEEPS and bmsp_krylov_solve refuses everything beyond.  The step kernels treat it like the ILU kinds: z, ph and sh are
-// vectors of their own, written by the application, followed by kStepDotRZ in CG.
-constexpr int kPcHook = BMSP_PC_ILU_SWEEPS + 1;
 
 // The scalars of one solve, device-resident.  `stopped` is what every kernel reads first; `status` is a BMSP_KRYLOV_* value.
 struct KrylovState {
@@ -33,7 +29,7 @@ struct KrylovState {
     int status, stopped;
     uint32_t ticket, pad;
 };
-// (the dot tree, the ticket hand-off and KrylovRecord: dot_tree.hip.h)
+// (the dot tree, the ticket hand-off, stop, residual_verdict, bb_step and KrylovRecord: dot_tree.hip.h)
 
 // bmsp_vec_dot, first level (and the second under TICKET)
 template <typename R, bool TICKET>
@@ -110,12 +106,6 @@ struct StepArgs {
     double tol2;        // fl(tol * tol), or negative under NO_CHECK
 };
 
-__device__ __forceinline__ void stop(KrylovState *S, int status)
-{
-    S->status = status;
-    S->stopped = 1;
-}
-
 // The residual dot of iteration k (0: of the start, which leaves no record).  True if the iteration goes on.
 template <typename R>
 __device__ __forceinline__ bool residual_step(const StepArgs<R> &a, double rr)
@@ -129,9 +119,7 @@ __device__ __forceinline__ bool residual_step(const StepArgs<R> &a, double rr)
             a.rec[a.k - 1].written = 1;
         }
     }
-    if (!__builtin_isfinite(rr)) stop(S, BMSP_KRYLOV_BREAKDOWN);
-    else if (rr <= S->thr) stop(S, BMSP_KRYLOV_CONVERGED);
-    else if (rr == 0.0) stop(S, BMSP_KRYLOV_BREAKDOWN);  // (NO_CHECK: thr < 0)
+    residual_verdict(S, rr);
     return !S->stopped;
 }
 
@@ -160,13 +148,10 @@ __device__ __forceinline__ void scalar_step(const StepArgs<R> &a, double s0, dou
     KrylovState *S = a.S;
     const bool none = a.pc == BMSP_PC_NONE;
     if (STEP == kStepBB) {
-        S->bb = s0;
-        const double thr = a.tol2 * s0;
-        S->thr = a.tol2 < 0.0 ? -1.0 : thr;
-        if (s0 == 0.0) return stop(S, BMSP_KRYLOV_CONVERGED);
-        if (!__builtin_isfinite(s0)) return stop(S, BMSP_KRYLOV_BREAKDOWN);
-        if (a.x) return;  // (x0 given: kStepR0 follows)
-        if (residual_step(a, s0) && (none || a.bicg)) rho_step(a, s0);
+        bb_step(S, s0, a.tol2, [&]() {
+            if (a.x) return;  // (x0 given: kStepR0 follows)
+            if (residual_step(a, s0) && (none || a.bicg)) rho_step(a, s0);
+        });
     } else if (STEP == kStepR0) {
         S->products++;
         if (residual_step(a, s0) && (none || a.bicg)) rho_step(a, s0);
@@ -342,173 +327,84 @@ std::mutex g_dot_mu;
 std::map<std::pair<int, hipStream_t>, DotScratch> g_dot_scratch;
 
 template <typename R>
-void run_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const KrylovHook *hook, const char *hook_name, const void *b,
-               void *x, int64_t m, double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+void run_solve(const SolveCall &c, int method)
 {
-    const int64_t n = A->num_rows;
-    const int kind = hook ? kPcHook : (pc ? pc->kind : BMSP_PC_NONE);
-    const bool bicg = method == BMSP_KRYLOV_BICGSTAB, checked = !no_check(tol), x0 = (flags & BMSP_KRYLOV_X0_GIVEN) != 0;
-    const bool ilu = kind == BMSP_PC_ILU_EXACT || kind == BMSP_PC_ILU_SWEEPS || kind == kPcHook;  // (applied through ilu_apply)
-    bmsp_matrix_s *F = ilu && !hook ? pc->F : nullptr;
+    bmsp_matrix_s *A = c.A;
+    const hipStream_t st = c.st;
+    const int64_t n = A->num_rows, m = c.cap;
+    const int kind = c.kind();
+    const bool bicg = method == BMSP_KRYLOV_BICGSTAB, checked = c.checked(), applied = c.applied();
     const int nvec = bicg ? 8 : 4;
     const int64_t chunks = chunks_of(n);
     // workspace: state | partials | diagonal | vectors | records
     const size_t vbytes = round256(sizeof(R) * (size_t)n);
     const size_t off_P = round256(sizeof(KrylovState)), off_d = off_P + round256(sizeof(double) * 2 * (size_t)chunks);
     const size_t off_v = off_d + vbytes, off_rec = off_v + vbytes * (size_t)nvec;
-    const size_t need = off_rec + (checked ? sizeof(KrylovRecord) * (size_t)m : 0);
-    if (need > A->krylov_ws_bytes) {
-        if (A->krylov_ws) BMSP_HIP(hipStreamSynchronize(st));  // (work enqueued on the old one has finished before it goes back to the pool)
-        A->krylov_ws.release();
-        A->krylov_ws_bytes = 0;
-        A->krylov_ws.alloc(need);
-        A->krylov_ws_bytes = need;
-    }
-    char *ws = (char *)A->krylov_ws;
+    char *ws = grow_workspace(A, off_rec + (checked ? sizeof(KrylovRecord) * (size_t)m : 0), st);
     StepArgs<R> a{};
     a.S = (KrylovState *)ws;
     a.rec = checked ? (KrylovRecord *)(ws + off_rec) : nullptr;
     a.P = (double *)(ws + off_P);
-    a.b = (const R *)b;
+    a.b = (const R *)c.b;
     a.d = (const R *)(ws + off_d);
-    a.x = (R *)x;
+    a.x = (R *)c.x;
     for (int j = 0; j < nvec; j++) a.v[j] = (R *)(ws + off_v + vbytes * (size_t)j);
     if (kind == BMSP_PC_NONE) {
         if (bicg) { a.v[kPh] = a.v[kP]; a.v[kSh] = a.v[kS]; }
         else a.v[kZ] = a.v[kR];
     }
     a.n = n; a.k = 0; a.chunks = (uint32_t)chunks; a.pc = kind; a.bicg = bicg ? 1 : 0;
-    a.tol2 = checked ? tol * tol : -1.0;
+    a.tol2 = c.tol2();
     a.ticket = finish_by_ticket(chunks) ? 1 : 0;
-    if (info) {
-        memset(info, 0, sizeof *info);
-        static const char *const names[4] = {"none", "jacobi", "ilu", "ilu_sweeps"};
-        snprintf(info->method, sizeof info->method, "%s+%s", bicg ? "bicgstab" : "cg", hook ? hook_name : names[kind]);
-        info->max_iterations = m;
-        info->workspace_bytes = (int64_t)A->krylov_ws_bytes;
-    }
-    const auto product = [&](const R *in, R *out) { spmv_op(A, op, 1.0, in, 0.0, out, st); };
-    // out = M^-1 in for the ILU kinds, through tmp: L then U; under op T the transposed factors, U^T then L^T.  A hooked solve: the hook,
-    // which gets the status word every kernel of the solver reads first.
-    const auto ilu_apply = [&](const R *in, R *tmp, R *out) {
-        if (hook) return (*hook)(in, out, &a.S->stopped, st);
-        const int first = op == BMSP_OP_T ? BMSP_FILL_UPPER : BMSP_FILL_LOWER;
-        for (int half = 0; half < 2; half++) {
-            const int fill = half == 0 ? first : 1 - first;
-            const int diag = fill == BMSP_FILL_LOWER ? BMSP_DIAG_UNIT : BMSP_DIAG_NON_UNIT;
-            const R *src = half == 0 ? in : tmp;
-            R *dst = half == 0 ? tmp : out;
-            if (kind == BMSP_PC_ILU_EXACT) spsv(F, op, fill, diag, 1.0, src, dst, st);
-            else spitsv(F, op, fill, diag, 1.0, src, dst, pc->sweeps, BMSP_ITSV_NO_CHECK, 0, nullptr, nullptr, st);
+    begin_info(c, bicg ? "bicgstab" : "cg");
+    const auto apply = [&](const R *in, R *tmp, R *out) { pc_apply(c, in, tmp, out, &a.S->stopped); };
+    // z = M^-1 r and rho' = dot(r, z), then the next p (CG; with BMSP_PC_NONE z is r and rho' came with the residual)
+    const auto next_p = [&]() {
+        if (kind == BMSP_PC_JACOBI) launch_step<R, kStepJacobi>(a, st);
+        else if (applied) {
+            apply(a.v[kR], a.v[kQ], a.v[kZ]);
+            launch_step<R, kStepDotRZ>(a, st);
         }
+        launch_step<R, kStepCgP>(a, st);
     };
     KrylovState hs{};
-    const auto read_state = [&]() {
-        BMSP_HIP(hipStreamSynchronize(st));
-        copy_d2h_staged(&hs, a.S, sizeof hs);
-    };
-    const size_t xbytes = sizeof(R) * (size_t)n;
-
-    // ---- the start ----
-    BMSP_HIP(hipMemsetAsync(a.S, 0, sizeof(KrylovState), st));
-    if (checked && m > 0) BMSP_HIP(hipMemsetAsync(a.rec, 0, sizeof(KrylovRecord) * (size_t)m, st));
-    {
-        StepArgs<R> s = a;
-        if (!x0) s.x = nullptr;  // (kStepBB: the start's residual is b's)
-        launch_step<R, kStepBB>(s, st);
-    }
-    bool finished = false;
-    if (checked) {
-        read_state();
-        finished = hs.stopped != 0;
-        if (finished && (hs.bb == 0.0 || !x0)) BMSP_HIP(hipMemsetAsync(x, 0, xbytes, st));
-    }
-    if (!finished) {
-        if (kind == BMSP_PC_JACOBI) matrix_diagonal(A, (void *)a.d, st);
-        if (x0) {
-            if (!checked) launch_step<R, kStepZeroX>(a, st);
-            product(a.x, a.v[3]);
+    const bool finished = solve_start(
+        c, a.S, a.rec, a.d, a.v[kR], hs,
+        [&]() {
+            StepArgs<R> s = a;
+            if (!c.x0()) s.x = nullptr;  // (kStepBB: the start's residual is b's)
+            launch_step<R, kStepBB>(s, st);
+        },
+        [&]() { launch_step<R, kStepZeroX>(a, st); },
+        [&]() {
+            product(c, a.x, a.v[3]);
             launch_step<R, kStepR0>(a, st);
-        } else {
-            BMSP_HIP(hipMemsetAsync(x, 0, xbytes, st));
-            BMSP_HIP(hipMemcpyAsync(a.v[kR], b, xbytes, hipMemcpyDeviceToDevice, st));
-        }
-        if (bicg) {
-            BMSP_HIP(hipMemcpyAsync(a.v[kRh], a.v[kR], xbytes, hipMemcpyDeviceToDevice, st));
-        } else {
-            if (kind == BMSP_PC_JACOBI) launch_step<R, kStepJacobi>(a, st);
-            else if (ilu) {
-                ilu_apply(a.v[kR], a.v[kQ], a.v[kZ]);
-                launch_step<R, kStepDotRZ>(a, st);
-            }
-            launch_step<R, kStepCgP>(a, st);
-        }
-    }
-    // ---- the iterations: `check` of them between two read-backs ----
-    const int64_t fixed = checked ? sweep_check_from_env("BMSP_KRYLOV_CHECK", 0) : m;  // (0: the ramp)
-    int64_t ramp = 1;
-    for (int64_t done = 0; done < m && !finished;) {
-        const int64_t check = fixed ? fixed : ramp;
-        ramp = ramp < kCheckRampMax ? 2 * ramp : kCheckRampMax;
-        const int64_t batch = check < m - done ? check : m - done;
-        for (int64_t k = done + 1; k <= done + batch; k++) {
+        });
+    if (!finished) {
+        if (bicg) BMSP_HIP(hipMemcpyAsync(a.v[kRh], a.v[kR], sizeof(R) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        else next_p();
+        solve_iterations(c, a.S, hs, [&](int64_t k) {
             a.k = k;
             if (!bicg) {
-                product(a.v[kP], a.v[kQ]);
+                product(c, a.v[kP], a.v[kQ]);
                 launch_step<R, kStepDotPQ>(a, st);
                 launch_step<R, kStepCgXR>(a, st);
-                if (k == m) break;  // (what follows prepares the next iteration)
-                if (kind == BMSP_PC_JACOBI) launch_step<R, kStepJacobi>(a, st);
-                else if (ilu) {
-                    ilu_apply(a.v[kR], a.v[kQ], a.v[kZ]);
-                    launch_step<R, kStepDotRZ>(a, st);
-                }
-                launch_step<R, kStepCgP>(a, st);
+                if (k < m) next_p();  // (prepares the next iteration)
             } else {
                 launch_step<R, kStepBiP>(a, st);
-                if (ilu) ilu_apply(a.v[kP], a.v[kSh], a.v[kPh]);
-                product(a.v[kPh], a.v[kV]);
+                if (applied) apply(a.v[kP], a.v[kSh], a.v[kPh]);
+                product(c, a.v[kPh], a.v[kV]);
                 launch_step<R, kStepDotRhV>(a, st);
                 launch_step<R, kStepBiSX>(a, st);
-                if (ilu) ilu_apply(a.v[kS], a.v[kT], a.v[kSh]);
-                product(a.v[kSh], a.v[kT]);
+                if (applied) apply(a.v[kS], a.v[kT], a.v[kSh]);
+                product(c, a.v[kSh], a.v[kT]);
                 launch_step<R, kStepDotTT>(a, st);
                 launch_step<R, kStepBiXR>(a, st);
             }
-        }
-        done += batch;
-        if (checked) {
-            read_state();
-            finished = hs.stopped != 0;
-        }
+        });
     }
-    if (!checked) {
-        if (info) {
-            info->iterations = m;
-            info->status = BMSP_KRYLOV_MAXITER;
-            info->relres = info->bnorm = -1.0;
-            info->products = (bicg ? 2 * m : m) + (x0 ? 1 : 0);
-            info->precond_applies = kind == BMSP_PC_NONE ? 0 : (bicg ? 2 * m : m);
-        }
-        return;
-    }
-    // the host decides by the device's predicate: the records it read say the same as the state
-    const int64_t its = hs.iterations;
-    std::vector<KrylovRecord> recs((size_t)(its > 0 ? its : 1));
-    if (its > 0) copy_d2h_staged(recs.data(), a.rec, sizeof(KrylovRecord) * (size_t)its);
-    const double last = its > 0 ? recs[(size_t)its - 1].rr : hs.rr;
-    int status = hs.stopped ? hs.status : BMSP_KRYLOV_MAXITER;
-    if (status != BMSP_KRYLOV_BREAKDOWN && hs.bb != 0.0) status = last <= hs.thr ? BMSP_KRYLOV_CONVERGED : BMSP_KRYLOV_MAXITER;
-    if (relres_history)
-        for (int64_t k = 0; k < its; k++) relres_history[k] = std::sqrt(recs[(size_t)k].rr / hs.bb);
-    if (info) {
-        info->iterations = its;
-        info->status = status;
-        info->bnorm = std::sqrt(hs.bb);
-        info->relres = hs.bb == 0.0 ? 0.0 : std::sqrt(last / hs.bb);
-        info->products = hs.products;
-        info->precond_applies = hs.applies;
-    }
+    if (!checked) return no_check_info(c, bicg ? 2 * m : m, bicg ? 2 * m : m);
+    checked_info(c, a.rec, hs);
 }
 
 }  // namespace
@@ -586,9 +482,8 @@ void krylov_check_args(int op, int method, const bmsp_precond *pc, int64_t max_i
     if (no_check(tol) && relres_history) fail(BMSP_ERR_INVALID, "relres_history must be NULL under BMSP_KRYLOV_NO_CHECK: nothing is read back");
 }
 
-void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc, const void *b, const void *x)
+void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc)
 {
-    if (b == x) fail(BMSP_ERR_INVALID, "d_x must not be d_b: b is read after x has been written");
     if (A->num_rows != A->num_cols) fail(BMSP_ERR_INVALID, "krylov_solve: matrix A must be square (it is %d x %d)", A->num_rows, A->num_cols);
     spmv_op_check_matrix(A, "krylov_solve");
     if (pc && (pc->kind == BMSP_PC_ILU_EXACT || pc->kind == BMSP_PC_ILU_SWEEPS)) {
@@ -603,33 +498,15 @@ void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc, const
     if (A->dtype == BMSP_F16) fail(BMSP_ERR_UNSUPPORTED, "krylov_solve: an F16 matrix A is not supported (the Krylov vectors would be fp16)");
 }
 
-void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const void *b, void *x, int64_t max_iter, double tol,
-                  int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
-{
-    const int64_t n = A->num_rows;  // (the arguments were checked at the C boundary: krylov_check_args, krylov_check_operands)
-    const int64_t m = max_iter ? max_iter : (n < kMaxIter ? n : kMaxIter);
-    if (n == 0) {
-        if (info) {
-            memset(info, 0, sizeof *info);
-            snprintf(info->method, sizeof info->method, "none (empty matrix)");
-            info->status = BMSP_KRYLOV_CONVERGED;
-        }
-        return;
-    }
-    if (A->dtype == BMSP_F64) run_solve<double>(A, op, method, pc, nullptr, nullptr, b, x, m, tol, flags, relres_history, info, st);
-    else run_solve<float>(A, op, method, pc, nullptr, nullptr, b, x, m, tol, flags, relres_history, info, st);
-}
-
-// bmsp_krylov_solve for op N with the preconditioner given as a callable (info->method: "<method>+<name>"); the arguments were checked
-// at the C boundary
-void krylov_solve_hooked(bmsp_matrix_s *A, int method, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
-                         double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st)
+// (the arguments were checked at the C boundary: krylov_check_args, krylov_check_operands)
+void krylov_solve(bmsp_matrix_s *A, int op, int method, const SolvePc &pc, const void *b, void *x, int64_t max_iter, double tol, int flags,
+                  double *relres_history, bmsp_krylov_info *info, hipStream_t st)
 {
     const int64_t n = A->num_rows;
-    if (n == 0) return krylov_solve(A, BMSP_OP_N, method, nullptr, b, x, max_iter, tol, flags, relres_history, info, st);
-    const int64_t m = max_iter ? max_iter : (n < kMaxIter ? n : kMaxIter);
-    if (A->dtype == BMSP_F64) run_solve<double>(A, BMSP_OP_N, method, nullptr, &hook, name, b, x, m, tol, flags, relres_history, info, st);
-    else run_solve<float>(A, BMSP_OP_N, method, nullptr, &hook, name, b, x, m, tol, flags, relres_history, info, st);
+    if (empty_solve(n, info)) return;
+    const SolveCall c{A, op, pc, b, x, cap_of(n, max_iter), tol, flags, relres_history, info, st};
+    if (A->dtype == BMSP_F64) run_solve<double>(c, method);
+    else run_solve<float>(c, method);
 }
 
 }  // namespace bmsp

@@ -5,7 +5,6 @@
 
 #include "mac_choice.h"
 #include "runtime.h"
-#include <functional>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -398,22 +397,24 @@ void vec_check_args(int64_t n, int vec_f64);
 void vec_dot(int64_t n, int vec_f64, const void *x, const void *y, double *result, hipStream_t st);
 void vec_axpby(int64_t n, int vec_f64, double a, const void *x, double b, void *y, hipStream_t st);
 void krylov_check_args(int op, int method, const bmsp_precond *pc, int64_t max_iter, double tol, int flags, const double *relres_history);
-void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc, const void *b, const void *x);
-void krylov_solve(bmsp_matrix_s *A, int op, int method, const bmsp_precond *pc, const void *b, void *x, int64_t max_iter, double tol,
-                  int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
-// out = M^-1 in, enqueued on the stream; `stopped` is the solve's status word on the device, which the hook's kernels read first
-using KrylovHook = std::function<void(const void *in, void *out, const int *stopped, hipStream_t st)>;
-void krylov_solve_hooked(bmsp_matrix_s *A, int method, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
-                         double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
-// gmres.hip: restarted GMRES for op(A) x = b, enqueued on `st` like the two solvers above; restart 0 means 30.  The hooked form is
-// bmsp_mg_solve_gmres's (op N, the preconditioner a callable).
+void krylov_check_operands(const bmsp_matrix_s *A, const bmsp_precond *pc);
+// The preconditioner of a solve: a public bmsp_precond (null: none) or, where `hook` is set, a handle's: out = M^-1 in enqueued on the
+// stream by hook(handle, ...), printed as `name` in info->method, op N only.  `stopped` is the solve's status word on the device, which
+// the hook's kernels read first.
+struct SolvePc {
+    const bmsp_precond *pc = nullptr;
+    void (*hook)(void *handle, const void *in, void *out, const int *stopped, hipStream_t st) = nullptr;
+    void *handle = nullptr;
+    const char *name = nullptr;
+};
+void krylov_solve(bmsp_matrix_s *A, int op, int method, const SolvePc &pc, const void *b, void *x, int64_t max_iter, double tol, int flags,
+                  double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+// gmres.hip: restarted GMRES for op(A) x = b, enqueued on `st` like the two solvers above; restart 0 means 30
 void gmres_check_args(int op, int restart, const bmsp_precond *pc, int64_t max_iter, double tol, int flags, const double *relres_history);
-void gmres_solve(bmsp_matrix_s *A, int op, const bmsp_precond *pc, int restart, const void *b, void *x, int64_t max_iter, double tol,
-                 int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
-void gmres_solve_hooked(bmsp_matrix_s *A, int restart, const KrylovHook &hook, const char *name, const void *b, void *x, int64_t max_iter,
-                        double tol, int flags, double *relres_history, bmsp_krylov_info *info, hipStream_t st);
+void gmres_solve(bmsp_matrix_s *A, int op, const SolvePc &pc, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags,
+                 double *relres_history, bmsp_krylov_info *info, hipStream_t st);
 // multigrid.hip: the V-cycle of a caller-supplied hierarchy (the operators borrowed; diagonals, the coarse inverse and the work vectors
-// owned by the handle), enqueued on `st`, and CG / BiCGStab for A[0] x = b preconditioned by it.  mg_create synchronises `st`.
+// owned by the handle), enqueued on `st`, and the cycle as the preconditioner of a solve.  mg_create synchronises `st`.
 void mg_check_args(int levels, double omega, int pre, int post, const void *d_coarse_inv);
 void mg_check_operands(int levels, bmsp_matrix_s *const *A, bmsp_matrix_s *const *P, bmsp_matrix_s *const *R, const void *d_coarse_inv,
                        int64_t ld_inv);
@@ -422,10 +423,8 @@ bmsp_mg_s *mg_create(int levels, bmsp_matrix_s *const *A, bmsp_matrix_s *const *
 void mg_free(bmsp_mg_s *mg);
 void mg_info(bmsp_mg_s *mg, bmsp_mg_info_t *info);
 void mg_vcycle(bmsp_mg_s *mg, const void *r, void *z, const int *stopped, hipStream_t st);
-void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-              bmsp_krylov_info *info, hipStream_t st);
-void mg_solve_gmres(bmsp_mg_s *mg, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                    bmsp_krylov_info *info, hipStream_t st);
+// the cycle as the preconditioner of a solve of A[0] x = b (*A: A[0]); builds the restriction views a first cycle would
+SolvePc mg_solve_pc(bmsp_mg_s *mg, hipStream_t st, bmsp_matrix_s **A);
 // fsai.hip: the factorised sparse approximate inverse of op(A) on S's lower-triangular pattern as a new matrix (tiles in layout
 // out_transposed) or into a matrix G with a legal pattern (both synchronise `st`), and the preconditioner handle z = G2^T (G1 r) by two
 // bmsp_spmv_op, with CG / BiCGStab / GMRES for A x = b on top.  fsai_create and fsai_update synchronise `st`.
@@ -441,10 +440,8 @@ void fsai_free(bmsp_fsai_s *f);
 void fsai_get_info(bmsp_fsai_s *f, bmsp_fsai_handle_info *info);
 void fsai_factors(bmsp_fsai_s *f, bmsp_matrix_s **G1, bmsp_matrix_s **G2);
 void fsai_apply(bmsp_fsai_s *f, const void *r, void *z, hipStream_t st);
-void fsai_solve(bmsp_fsai_s *f, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                bmsp_krylov_info *info, hipStream_t st);
-void fsai_solve_gmres(bmsp_fsai_s *f, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                      bmsp_krylov_info *info, hipStream_t st);
+// the handle as the preconditioner of a solve of A x = b (*A: its A); rebuilds the views of the factors if they were dropped
+SolvePc fsai_solve_pc(bmsp_fsai_s *f, hipStream_t st, bmsp_matrix_s **A);
 // eager construction of the cached derived structures (bmsp_matrix_prepare)
 void prepare_spmv(bmsp_matrix_s *m, hipStream_t st);
 void prepare_spgemm_operand(bmsp_matrix_s *m, hipStream_t st);

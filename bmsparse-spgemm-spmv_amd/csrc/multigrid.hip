@@ -490,20 +490,15 @@ static void ensure_restriction_views(bmsp_mg_s *mg, hipStream_t st)
     }
 }
 
-void mg_solve(bmsp_mg_s *mg, int method, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-              bmsp_krylov_info *info, hipStream_t st)
+SolvePc mg_solve_pc(bmsp_mg_s *mg, hipStream_t st, bmsp_matrix_s **A)
 {
     ensure_restriction_views(mg, st);
-    const KrylovHook hook = [mg](const void *in, void *out, const int *stopped, hipStream_t s) { mg_vcycle(mg, in, out, stopped, s); };
-    krylov_solve_hooked(mg->A[0], method, hook, "mg", b, x, max_iter, tol, flags, relres_history, info, st);
-}
-
-void mg_solve_gmres(bmsp_mg_s *mg, int restart, const void *b, void *x, int64_t max_iter, double tol, int flags, double *relres_history,
-                    bmsp_krylov_info *info, hipStream_t st)
-{
-    ensure_restriction_views(mg, st);
-    const KrylovHook hook = [mg](const void *in, void *out, const int *stopped, hipStream_t s) { mg_vcycle(mg, in, out, stopped, s); };
-    gmres_solve_hooked(mg->A[0], restart, hook, "mg", b, x, max_iter, tol, flags, relres_history, info, st);
+    *A = mg->A[0];
+    SolvePc pc;
+    pc.hook = [](void *h, const void *in, void *out, const int *stopped, hipStream_t s) { mg_vcycle((bmsp_mg_s *)h, in, out, stopped, s); };
+    pc.handle = mg;
+    pc.name = "mg";
+    return pc;
 }
 
 }  // namespace bmsp

@@ -1190,28 +1190,10 @@ def krylov_solve(A, b, method="cg", precond=None, op="N", max_iter=0, tol=1e-6, 
     "bnorm", "products", "precond_applies", "workspace_bytes"}, history = the relative residual of every iteration (float64)."""
     if method not in _METHODS:
         raise ValueError("method must be 'cg' or 'bicgstab' (got %r)" % (method,))
-    pc, keep = _precond(precond)
+    pc, keep = _precond(precond)  # (keep: the factor lives until the call has returned)
     i = A.info()
-    vt = np.dtype(OUT_DTYPE[i["dtype"]])
-    if b.dtype != vt or b.n < i["num_rows"]:
-        raise ValueError("b must hold %d entries of %s" % (i["num_rows"], vt.name))
-    if x is None:
-        if x0_given:
-            raise ValueError("x0_given needs x")
-        x = DeviceArray(i["num_rows"], vt)
-    elif x.dtype != vt or x.n < i["num_rows"]:
-        raise ValueError("x must hold %d entries of %s" % (i["num_rows"], vt.name))
-    info = KrylovInfo()
-    hist = None
-    if history:
-        cap = int(max_iter) if max_iter else min(i["num_rows"], 1 << 20)
-        hist = np.zeros(max(cap, 1), np.float64)
-    check(lib().bmsp_krylov_solve(A.h, _op(op), _METHODS[method], C.byref(pc) if pc is not None else None, b.ptr, x.ptr, int(max_iter),
-                                  float(tol), KRYLOV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info),
-                                  stream))
-    del keep
-    d = info.as_dict()
-    return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+    return _solve_call(i["num_rows"], np.dtype(OUT_DTYPE[i["dtype"]]), b, x, x0_given, max_iter, tol, history, stream,
+                       lambda *tail: lib().bmsp_krylov_solve(A.h, _op(op), _METHODS[method], C.byref(pc) if pc is not None else None, *tail))
 
 
 def _gmres_restart(method):
@@ -1240,21 +1222,26 @@ def _solve_vectors(n, vt, b, x, x0_given, max_iter, history):
     return x, hist
 
 
+def _solve_call(n, vt, b, x, x0_given, max_iter, tol, history, stream, call):
+    """the tail every solve shares: the vector checks, then call(d_b, d_x, max_iter, tol, flags, relres_history, info, stream) -- the
+    arguments every bmsp_*_solve* ends with -- and (x, info) or (x, info, history) from what it left"""
+    x, hist = _solve_vectors(n, vt, b, x, x0_given, max_iter, history)
+    info = KrylovInfo()
+    check(call(b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None,
+               C.byref(info), stream))
+    d = info.as_dict()
+    return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+
+
 def gmres_solve(A, b, precond=None, op="N", restart=30, max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
     """Solves op(A) * x = b on the device by restarted GMRES (bmsp_gmres_solve): right-preconditioned GMRES(restart), restart 1 .. 256
     (0: 30), the basis orthogonalised by classical Gram-Schmidt applied twice.  One product and one preconditioner application per
     iteration, plus one product per restart.  Everything else -- A, b, precond, op, max_iter, tol, KRYLOV_NO_CHECK, x, x0_given, history,
     stream and the results -- is krylov_solve's; info["method"] is "gmres(<m>)+<preconditioner>"."""
-    pc, keep = _precond(precond)
+    pc, keep = _precond(precond)  # (keep: the factor lives until the call has returned)
     i = A.info()
-    x, hist = _solve_vectors(i["num_rows"], np.dtype(OUT_DTYPE[i["dtype"]]), b, x, x0_given, max_iter, history)
-    info = KrylovInfo()
-    check(lib().bmsp_gmres_solve(A.h, _op(op), C.byref(pc) if pc is not None else None, int(restart), b.ptr, x.ptr, int(max_iter),
-                                 float(tol), KRYLOV_X0_GIVEN if x0_given else 0, hist.ctypes.data if history else None, C.byref(info),
-                                 stream))
-    del keep
-    d = info.as_dict()
-    return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+    return _solve_call(i["num_rows"], np.dtype(OUT_DTYPE[i["dtype"]]), b, x, x0_given, max_iter, tol, history, stream,
+                       lambda *tail: lib().bmsp_gmres_solve(A.h, _op(op), C.byref(pc) if pc is not None else None, int(restart), *tail))
 
 
 class Multigrid:
@@ -1314,31 +1301,12 @@ class Multigrid:
         """A[0] * x = b by CG or BiCGStab preconditioned by one cycle (bmsp_mg_solve): krylov_solve's arguments and results.  method
         "gmres": GMRES(restart) preconditioned by one cycle (bmsp_mg_solve_gmres), which takes any cycle"""
         if method == "gmres":
-            x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
-            info = KrylovInfo()
-            check(lib().bmsp_mg_solve_gmres(self.h, int(restart), b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
-                                            hist.ctypes.data if history else None, C.byref(info), stream))
-            d = info.as_dict()
-            return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+            return _solve_call(self.n, self.dtype, b, x, x0_given, max_iter, tol, history, stream,
+                               lambda *tail: lib().bmsp_mg_solve_gmres(self.h, int(restart), *tail))
         if method not in _METHODS:
             raise ValueError("method must be 'cg', 'bicgstab' or 'gmres' (got %r)" % (method,))
-        if b.dtype != self.dtype or b.n < self.n:
-            raise ValueError("b must hold %d entries of %s" % (self.n, self.dtype.name))
-        if x is None:
-            if x0_given:
-                raise ValueError("x0_given needs x")
-            x = DeviceArray(self.n, self.dtype)
-        elif x.dtype != self.dtype or x.n < self.n:
-            raise ValueError("x must hold %d entries of %s" % (self.n, self.dtype.name))
-        info = KrylovInfo()
-        hist = None
-        if history:
-            cap = int(max_iter) if max_iter else min(self.n, 1 << 20)
-            hist = np.zeros(max(cap, 1), np.float64)
-        check(lib().bmsp_mg_solve(self.h, _METHODS[method], b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
-                                  hist.ctypes.data if history else None, C.byref(info), stream))
-        d = info.as_dict()
-        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+        return _solve_call(self.n, self.dtype, b, x, x0_given, max_iter, tol, history, stream,
+                           lambda *tail: lib().bmsp_mg_solve(self.h, _METHODS[method], *tail))
 
 
 def fsai(A, S, op="N", scale="sqrt", transposed=None, pivot=False, stream=None):
@@ -1460,21 +1428,13 @@ class Fsai:
             return self.solve_gmres(b, restart, max_iter, tol, x, x0_given, history, stream)
         if method not in _METHODS:
             raise ValueError("method must be 'cg', 'bicgstab' or 'gmres' (got %r)" % (method,))
-        x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
-        info = KrylovInfo()
-        check(lib().bmsp_fsai_solve(self.h, _METHODS[method], b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
-                                    hist.ctypes.data if history else None, C.byref(info), stream))
-        d = info.as_dict()
-        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+        return _solve_call(self.n, self.dtype, b, x, x0_given, max_iter, tol, history, stream,
+                           lambda *tail: lib().bmsp_fsai_solve(self.h, _METHODS[method], *tail))
 
     def solve_gmres(self, b, restart=30, max_iter=0, tol=1e-6, x=None, x0_given=False, history=False, stream=None):
         """A x = b by GMRES(restart) preconditioned by this (bmsp_fsai_solve_gmres): gmres_solve's arguments and results"""
-        x, hist = _solve_vectors(self.n, self.dtype, b, x, x0_given, max_iter, history)
-        info = KrylovInfo()
-        check(lib().bmsp_fsai_solve_gmres(self.h, int(restart), b.ptr, x.ptr, int(max_iter), float(tol), KRYLOV_X0_GIVEN if x0_given else 0,
-                                          hist.ctypes.data if history else None, C.byref(info), stream))
-        d = info.as_dict()
-        return (x, d, hist[:d["iterations"]].copy()) if history else (x, d)
+        return _solve_call(self.n, self.dtype, b, x, x0_given, max_iter, tol, history, stream,
+                           lambda *tail: lib().bmsp_fsai_solve_gmres(self.h, int(restart), *tail))
 
 
 def _spsm_strides(k, ldb, ldx):

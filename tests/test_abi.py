@@ -66,6 +66,15 @@ def test_host_mac_choice_table(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
 
 
+def test_host_solve_schedule(tmp_path):
+    """the iteration cap and the batches between two read-backs of a solve (csrc/solve_schedule.h, no HIP): the ramp, a fixed check, the
+    cut at the cap, NO_CHECK's single batch"""
+    exe = str(tmp_path / "solve_schedule")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", os.path.join(REPO, "tests", "host_solve_schedule_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout
+
+
 def test_host_handle_lifetimes(tmp_path):
     """what a handle caches (csrc/matrix.h, no HIP linked) against a counting pool: the two resets of bmsp_matrix_invalidate, re-assigned
     owners, delete with either ownership, buffers moved out; and the program filled as many owners as the struct declares"""
