@@ -47,6 +47,37 @@ BMSP_HD int tile_transposed_pos(int p) { return ((p & 7) << 3) | (p >> 3); }
 // positions 9k: row k, column k of a tile in either layout
 BMSP_HD uint64_t tile_diagonal_mask() { return 0x8040201008040201ull; }
 
+// Band selection (select.hip).  With d = c - r the in-tile diagonal of position 8r + c, a whole-row shift of the lower triangle
+// (d <= 0) is the triangle d <= k, k <= 0: rows that leave the word are gone, nothing wraps into a neighbouring row.  The triangles with
+// k > 0 are the complements of the upper triangle (d >= 0) shifted the other way.
+//   tile_lower_mask(k): the positions with c - r <= k; nothing below k = -7, everything from k = 7
+BMSP_HD uint64_t tile_lower_mask(int64_t k)
+{
+    if (k <= -8) return 0;
+    if (k >= 7) return ~0ull;
+    return k <= 0 ? 0x80C0E0F0F8FCFEFFull >> (8 * (int)-k) : ~(0xFF7F3F1F0F070301ull << (8 * ((int)k + 1)));
+}
+// the 64 positions 8r + c with dlo <= c - r <= dhi (the arguments clamped to [-8, 8]; dlo > dhi: none).  The same band of a column-major
+// tile (pos = 8c + r) is tile_band_mask(-dhi, -dlo) = tile_transpose(tile_band_mask(dlo, dhi)).
+BMSP_HD uint64_t tile_band_mask(int64_t dlo, int64_t dhi)
+{
+    dlo = dlo < -8 ? -8 : dlo > 8 ? 8 : dlo;
+    dhi = dhi < -8 ? -8 : dhi > 8 ? 8 : dhi;
+    return tile_lower_mask(dhi) & ~tile_lower_mask(dlo - 1);
+}
+// A tile at block distance delta = block_col - block_row holds the matrix diagonals 8*delta - 7 .. 8*delta + 7 (col - row of its
+// entries): the band lo <= col - row <= hi misses it, holds all of it, or cuts it.  |lo|, |hi| <= 2^36 and |delta| < 2^32: no overflow.
+BMSP_HD bool tile_band_misses(int64_t delta, int64_t lo, int64_t hi) { return 8 * delta + 7 < lo || 8 * delta - 7 > hi; }
+BMSP_HD bool tile_band_covers(int64_t delta, int64_t lo, int64_t hi) { return 8 * delta - 7 >= lo && 8 * delta + 7 <= hi; }
+// the bits of bmp (a tile at block distance delta, column-major when colmajor) whose entries lie in the band
+BMSP_HD uint64_t tile_band_select(uint64_t bmp, int64_t delta, int64_t lo, int64_t hi, int colmajor)
+{
+    if (tile_band_misses(delta, lo, hi)) return 0;
+    if (tile_band_covers(delta, lo, hi)) return bmp;
+    const int64_t dlo = lo - 8 * delta, dhi = hi - 8 * delta;
+    return bmp & (colmajor ? tile_band_mask(-dhi, -dlo) : tile_band_mask(dlo, dhi));
+}
+
 // first stored position of a non-empty mask, removed from it: `while (m) { p = tile_pop_first(m); .. }` visits the stored positions in
 // ascending order, the order of the tile's values
 BMSP_HD int tile_pop_first(uint64_t &m)

@@ -411,6 +411,28 @@ int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream)
     BMSP_API_END
 }
 
+int bmsp_matrix_select_band(bmsp_matrix_t A, int64_t lo, int64_t hi, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
+                            bmsp_select_stats *stats)
+{
+    BMSP_API_BEGIN
+    select_check_args(flags, out_transposed, out, stats);
+    need(A, "matrix A");
+    load_kernels();
+    select_band(A, lo, hi, flags, out_transposed, as_stream(stream), out, stats);
+    BMSP_API_END
+}
+
+int bmsp_matrix_select_mask(bmsp_matrix_t A, bmsp_matrix_t M, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
+                            bmsp_select_stats *stats)
+{
+    BMSP_API_BEGIN
+    select_check_args(flags, out_transposed, out, stats);
+    need(A, "matrix A"); need(M, "matrix M");
+    load_kernels();
+    select_mask(A, M, flags, out_transposed, as_stream(stream), out, stats);
+    BMSP_API_END
+}
+
 int bmsp_matrix_diagonal(bmsp_matrix_t A, void *d_diag, void *stream)
 {
     BMSP_API_BEGIN

@@ -335,6 +335,13 @@ void prune_check_args(int rule, double tol, int flags, int out_transposed);
 void prune_matrix(bmsp_matrix_s *A, int rule, double tol, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
                   bmsp_prune_stats *stats);
 void row_absmax(bmsp_matrix_s *A, void *d_rowmax, hipStream_t st);
+// select.hip: *out = A's entries in the band lo <= col - row <= hi / at the coordinates M stores (or, under BMSP_SELECT_COMPLEMENT, the
+// others), tiles in layout out_transposed, and / or the counts
+void select_check_args(int flags, int out_transposed, const void *out, const void *stats);
+void select_band(bmsp_matrix_s *A, int64_t lo, int64_t hi, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
+                 bmsp_select_stats *stats);
+void select_mask(bmsp_matrix_s *A, bmsp_matrix_s *M, int flags, int out_transposed, hipStream_t st, bmsp_matrix_s **out,
+                 bmsp_select_stats *stats);
 // diag.hip: the diagonal as a vector, a diagonal matrix from a vector, out = diag(l) * A * diag(r) as a new matrix (tiles in layout
 // out_transposed) or into A itself / a matrix made from A by scale_matrix or a layout conversion
 void scale_check_args(const void *d_left, const void *d_right, int flags, int out_transposed);

@@ -13,12 +13,9 @@
 //           n tiles costs n / 64 (G = 1) or n / 8 (G = 8) atomics per row, not n.  Max is exact and order-independent.
 //   mark    G lanes per tile: the kept bitmap in A's layout (G = 8: a lane per bitmap byte, OR'd across the eight lanes).  The diagonal
 //           of a tile with block_row == block_col is the positions 0, 9, .., 63 in either layout.
-//   scan    one exclusive scan of {tile kept ? 1 : 0 (low 32 bits), kept values (high 32 bits)}: slot and value offset of every kept
-//           tile at once (a transposed bitmap has the same popcount, so the offsets need no second scan).  The total is read back: the one
-//           synchronisation in the middle; count-only calls end here.
-//   place   G lanes per tile of A: a kept tile writes its key, kept bitmap (transposed when the layout flips) and offset at its slot and
-//           compacts its kept values there; values move as raw bits.
-#include "tile_pass.hip.h"
+//   scan, place   the compaction selection shares (tile_compact.hip.h): slot and value offset of every kept tile in one scan, whose total
+//           is read back (count-only calls end there), then the move of the kept tiles and values as raw bits.
+#include "tile_compact.hip.h"
 #include <cmath>
 
 namespace bmsp {
@@ -121,65 +118,6 @@ __global__ __launch_bounds__(kThreads) void prune_mark_kernel(const uint64_t *__
     if (live && t == 0) kept[j] = keep;
 }
 
-// {tile kept (low 32 bits), kept values (high 32 bits)} of tile j; 0 at j == nb
-struct KeptIn {
-    const uint64_t *kept;
-    uint64_t nb;
-    __device__ uint64_t operator()(uint64_t j) const
-    {
-        if (j >= nb) return 0;
-        const uint64_t b = kept[j];
-        return (uint64_t)(b != 0) | (uint64_t)popc64(b) << 32;
-    }
-};
-
-struct KeptOut {
-    uint64_t *pos;  // nb + 1: {output slot, output value offset} of tile j; the totals at nb
-    uint64_t nb;
-    uint64_t *total;  // host scalar
-    __device__ void operator()(uint64_t j, uint64_t ex) const
-    {
-        pos[j] = ex;
-        if (j == nb) *total = ex;
-    }
-};
-
-// A's tiles [0, nb): a kept tile goes to its slot with its kept values; index nb writes the terminal offset
-template <typename T, int G>
-__global__ __launch_bounds__(kThreads) void prune_place_kernel(const uint64_t *__restrict__ a_keys, const uint64_t *__restrict__ a_bmps,
-                                                               const uint64_t *__restrict__ a_off, const T *__restrict__ a_vals,
-                                                               const uint64_t *__restrict__ kept, const uint64_t *__restrict__ pos, uint64_t nb,
-                                                               int flip, uint64_t *__restrict__ o_keys, uint64_t *__restrict__ o_bmps,
-                                                               uint64_t *__restrict__ o_off, T *__restrict__ o_vals)
-{
-    const uint64_t gid = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const uint64_t j = gid / G;
-    const int t = (int)(gid % G);
-    if (j > nb) return;
-    const uint64_t w = pos[j];
-    const uint64_t c = (uint32_t)w, off = w >> 32;
-    if (j == nb) {
-        if (t == 0) o_off[c] = off;
-        return;
-    }
-    const uint64_t kb = kept[j];
-    if (!kb) return;
-    const uint64_t ib = a_bmps[j];
-    const uint64_t ob = flip ? tile_transpose(kb) : kb;
-    if (t == 0) {
-        o_keys[c] = a_keys[j];
-        o_bmps[c] = ob;
-        o_off[c] = off;
-    }
-    uint64_t m = G == 1 ? ob : ob & tile_byte_mask(t);
-    T *dst = o_vals + off + (G == 1 ? 0 : tile_rank(ob, 8 * t));
-    const T *src = a_vals + a_off[j];
-    while (m) {
-        const int p = tile_pop_first(m);
-        *dst++ = src[tile_rank(ib, flip ? tile_transposed_pos(p) : p)];
-    }
-}
-
 template <typename S>
 void launch_row_absmax(int g, const bmsp_matrix_s *A, int64_t num_rows, void *rowmax, hipStream_t st)
 {
@@ -201,25 +139,6 @@ void launch_mark(int g, const bmsp_matrix_s *A, int rule, double tol, int flags,
         hipLaunchKernelGGL((prune_mark_kernel<S, decltype(lanes)::value>), grid, dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets,
                            (const S *)A->values, nb, A->transposed, rule, tol, kd, (const R *)rowmax, kept);
     });
-}
-
-template <typename T>
-void launch_place(int g, const bmsp_matrix_s *A, const uint64_t *kept, const uint64_t *pos, bmsp_matrix_s *out, hipStream_t st)
-{
-    const uint64_t nb = (uint64_t)A->block_num;
-    const int flip = A->transposed != out->transposed;
-    launch_lane_group(g, nb + 1, [&](auto lanes, dim3 grid) {  // (index nb: the terminal offset)
-        hipLaunchKernelGGL((prune_place_kernel<T, decltype(lanes)::value>), grid, dim3(kThreads), 0, st, A->keys, A->bmps, A->offsets,
-                           (const T *)A->values, kept, pos, nb, flip, out->keys, out->bmps, out->offsets, (T *)out->values);
-    });
-}
-
-void check_source(const bmsp_matrix_s *A, const char *what)
-{
-    refuse_view(A, what);
-    // slots and kept values are counted in the two 32-bit halves of one scan word
-    if (A->block_num >= 0xffffffffll) fail(BMSP_ERR_LIMIT, "%s: %lld tiles exceed the 32-bit slot count", what, (long long)A->block_num);
-    if (A->nnz >= (1ll << 32)) fail(BMSP_ERR_LIMIT, "%s: nnz %lld exceeds the 32-bit value count", what, (long long)A->nnz);
 }
 
 // zeroes `rowmax` (`entries` of A's row-maximum type) and fills its first num_rows entries
@@ -247,7 +166,7 @@ void prune_check_args(int rule, double tol, int flags, int out_transposed)
 
 void row_absmax(bmsp_matrix_s *A, void *d_rowmax, hipStream_t st)
 {
-    check_source(A, "row_absmax");
+    check_compact_source(A, "row_absmax");
     compute_row_absmax(A, d_rowmax, A->num_rows, st);
 }
 
@@ -257,41 +176,18 @@ void prune_matrix(bmsp_matrix_s *A, int rule, double tol, int flags, int out_tra
 {
     prune_check_args(rule, tol, flags, out_transposed);
     if (!out && !stats) fail(BMSP_ERR_INVALID, "prune: out and stats are both null");
-    check_source(A, "prune");
+    check_compact_source(A, "prune");
     const uint64_t nb = (uint64_t)A->block_num;
     const int g = lane_group(A->nnz, A->block_num, "BMSP_PRUNE_LANES");
-    DevBuf<uint64_t> kept(nb), pos(nb + 1);  // temporaries: back to the pool after the synchronisation at the end
-    DevBuf<uint64_t> rowmax;                 // (holds floats for F32 / F16)
+    DevBuf<uint64_t> kept(nb);  // temporaries: back to the pool after the synchronisation at the end of compact_tiles
+    DevBuf<uint64_t> rowmax;    // (holds floats for F32 / F16)
     if (rule == BMSP_PRUNE_ROW_REL) {
         const int64_t padded = A->num_block_rows() * 8;  // every row a key can name
         rowmax.alloc((size_t)padded);
         compute_row_absmax(A, rowmax.p, padded, st);
     }
     if (nb) dispatch_dtype(A->dtype, [&](auto s) { launch_mark<decltype(s)>(g, A, rule, tol, flags, rowmax.p, kept.p, st); });
-    HostScalar<uint64_t> total;
-    device_exclusive_scan<uint64_t>(KeptIn{kept.p, nb}, KeptOut{pos.p, nb, total.dev()}, nb + 1, st);
-    const uint64_t t = total.wait(st);
-    const uint64_t nc = (uint32_t)t, nnz_out = t >> 32;
-    if (stats) {
-        stats->nnz_in = A->nnz; stats->blocks_in = A->block_num;
-        stats->nnz_out = (int64_t)nnz_out; stats->blocks_out = (int64_t)nc;
-    }
-    if (!out) {
-        BMSP_HIP(hipStreamSynchronize(st));  // the temporaries go back to the pool
-        return;
-    }
-    auto m = make_matrix();
-    m->num_rows = A->num_rows; m->num_cols = A->num_cols; m->dtype = A->dtype; m->transposed = out_transposed;
-    m->block_num = (int64_t)nc;
-    m->nnz = (int64_t)nnz_out;
-    alloc_tile_arrays(m.get(), nc);
-    alloc_values(m.get(), nnz_out);
-    // the lane group of the move follows what is left of the tiles
-    const int gp = lane_group(m->nnz, m->block_num, "BMSP_PRUNE_LANES");
-    dispatch_width(m->dtype, [&](auto width) { launch_place<decltype(width)>(gp, A, kept.p, pos.p, m.get(), st); });
-    ensure_rowptr(m.get(), st);
-    BMSP_HIP(hipStreamSynchronize(st));
-    *out = m.release();
+    compact_tiles(A, kept.p, out_transposed, "BMSP_PRUNE_LANES", st, out, stats);
 }
 
 }  // namespace bmsp

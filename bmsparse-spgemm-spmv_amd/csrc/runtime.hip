@@ -187,6 +187,7 @@ void warm_comm(hipStream_t st);
 void warm_transpose(hipStream_t st);
 void warm_add(hipStream_t st);
 void warm_prune(hipStream_t st);
+void warm_select(hipStream_t st);
 void warm_diag(hipStream_t st);
 void warm_spmv_op(hipStream_t st);
 void warm_sddmm(hipStream_t st);
@@ -233,6 +234,7 @@ void load_kernels()
     warm_transpose(nullptr);
     warm_add(nullptr);
     warm_prune(nullptr);
+    warm_select(nullptr);
     warm_diag(nullptr);
     warm_spmv_op(nullptr);
     warm_sddmm(nullptr);

@@ -21,6 +21,8 @@ SORT_AUTO, SORT_SEGMENTED, SORT_GLOBAL = 0, 1, 2
 SPMV_DEFAULT, SPMV_BATCHED = 0, 1
 PRUNE_ABS, PRUNE_ROW_REL = 0, 1
 PRUNE_KEEP_DIAGONAL = 1
+SELECT_COMPLEMENT = 1
+BAND_MIN, BAND_MAX = -(1 << 63), (1 << 63) - 1
 SCALE_DIV_LEFT, SCALE_DIV_RIGHT = 1, 2
 OP_N, OP_T = 0, 1
 SDDMM_MUL_S = 1
@@ -56,7 +58,7 @@ SYMBOLS = [
     "bmsp_matrix_from_mtx", "bmsp_matrix_from_coo", "bmsp_matrix_from_coo_device", "bmsp_matrix_from_arrays",
     "bmsp_matrix_save", "bmsp_matrix_load", "bmsp_matrix_free", "bmsp_matrix_prepare", "bmsp_matrix_invalidate", "bmsp_matrix_info", "bmsp_matrix_arrays", "bmsp_matrix_block_row_ptr",
     "bmsp_matrix_transpose", "bmsp_matrix_convert_layout", "bmsp_matrix_copy_values", "bmsp_matrix_add", "bmsp_matrix_add_values",
-    "bmsp_matrix_prune", "bmsp_matrix_row_absmax",
+    "bmsp_matrix_prune", "bmsp_matrix_row_absmax", "bmsp_matrix_select_band", "bmsp_matrix_select_mask",
     "bmsp_matrix_diagonal", "bmsp_matrix_from_diagonal", "bmsp_matrix_scale", "bmsp_matrix_scale_values",
     "bmsp_matrix_to_coo_host", "bmsp_matrix_to_coo_device", "bmsp_matrix_to_csr_device", "bmsp_matrix_from_csr_device", "bmsp_matrix_compare", "bmsp_matrix_compare_device", "bmsp_spmv", "bmsp_spmv_launch_info", "bmsp_spmv_chunk_layout", "bmsp_spmv_op", "bmsp_spmv_op_launch_info", "bmsp_spmv_op_plan_items", "bmsp_spsv_analyse", "bmsp_spsv", "bmsp_spsv_plan", "bmsp_spsm", "bmsp_spsm_launch_info", "bmsp_spitsv", "bmsp_matrix_ilu0", "bmsp_matrix_ilu0_values", "bmsp_vec_dot", "bmsp_vec_axpby", "bmsp_matrix_color_blocks", "bmsp_matrix_permute_blocks", "bmsp_vec_permute_blocks", "bmsp_matrix_aggregate", "bmsp_matrix_from_aggregates", "bmsp_krylov_solve", "bmsp_gmres_solve", "bmsp_mg_create", "bmsp_mg_free", "bmsp_mg_info", "bmsp_mg_vcycle", "bmsp_mg_solve", "bmsp_mg_solve_gmres", "bmsp_matrix_fsai", "bmsp_matrix_fsai_values", "bmsp_fsai_create", "bmsp_fsai_update", "bmsp_fsai_free", "bmsp_fsai_get_info", "bmsp_fsai_factors", "bmsp_fsai_apply", "bmsp_fsai_solve", "bmsp_fsai_solve_gmres", "bmsp_sddmm", "bmsp_sddmm_values", "bmsp_sddmm_launch_info", "bmsp_spgemm_masked", "bmsp_spgemm_masked_values", "bmsp_spgemm_masked_launch_info", "bmsp_spmm", "bmsp_spmm_launch_info", "bmsp_spmm_op", "bmsp_spmm_op_launch_info", "bmsp_spgemm", "bmsp_spgemm_symbolic", "bmsp_spgemm_numeric", "bmsp_selftest_mfma_layout", "bmsp_selftest_mfma_f32_chain", "bmsp_selftest_tile_product", "bmsp_selftest_mfma_f32_cancel", "bmsp_segsort_u64",
     "bmsp_partition_rows", "bmsp_matrix_row_panel", "bmsp_matrix_concat_panels",
@@ -89,6 +91,9 @@ class PruneStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SelectStats = PruneStats  # bmsp_select_stats is bmsp_prune_stats
 
 
 class SpmvOpInfo(C.Structure):
@@ -284,6 +289,8 @@ def lib():
         L.bmsp_matrix_add_values.argtypes = [C.c_double, vp, C.c_double, vp, vp, vp]
         L.bmsp_matrix_prune.argtypes = [vp, i, C.c_double, i, i, vp, p(vp), p(PruneStats)]
         L.bmsp_matrix_row_absmax.argtypes = [vp, vp, vp]
+        L.bmsp_matrix_select_band.argtypes = [vp, C.c_int64, C.c_int64, i, i, vp, p(vp), p(SelectStats)]
+        L.bmsp_matrix_select_mask.argtypes = [vp, vp, i, i, vp, p(vp), p(SelectStats)]
         L.bmsp_matrix_diagonal.argtypes = [vp, vp, vp]
         L.bmsp_matrix_from_diagonal.argtypes = [i, i, vp, i, i, vp, p(vp)]
         L.bmsp_matrix_scale.argtypes = [vp, vp, vp, i, i, vp, p(vp)]
@@ -600,6 +607,22 @@ class BmSpMatrix:
         """(this matrix without the entries the rule drops, stats dict): pybmsp.prune"""
         return prune(self, tol, rule, keep_diagonal, transposed, stream)
 
+    def tril(self, k=0, transposed=None, stream=None):
+        """the stored entries with col - row <= k as a new matrix: pybmsp.tril"""
+        return tril(self, k, transposed, stream)
+
+    def triu(self, k=0, transposed=None, stream=None):
+        """the stored entries with col - row >= k as a new matrix: pybmsp.triu"""
+        return triu(self, k, transposed, stream)
+
+    def band(self, lo=None, hi=None, complement=False, transposed=None, stream=None):
+        """the stored entries with lo <= col - row <= hi (complement: the others) as a new matrix: pybmsp.select_band without the stats"""
+        return select_band(self, lo, hi, complement, transposed, stream)[0]
+
+    def mask(self, M, complement=False, transposed=None, stream=None):
+        """the stored entries at the coordinates M stores (complement: does not store) as a new matrix: pybmsp.select_mask without the stats"""
+        return select_mask(self, M, complement, transposed, stream)[0]
+
     def diagonal(self, stream=None):
         """the diagonal as a DeviceArray of min(num_rows, num_cols) entries, +0 where (i, i) is not stored: pybmsp.diagonal"""
         return diagonal(self, stream)
@@ -813,6 +836,63 @@ def row_absmax(A, stream=None):
     out = DeviceArray(i["num_rows"], OUT_DTYPE[i["dtype"]])
     check(lib().bmsp_matrix_row_absmax(A.h, out.ptr, stream))
     return out
+
+
+def _band_bounds(lo, hi):
+    return BAND_MIN if lo is None else int(lo), BAND_MAX if hi is None else int(hi)
+
+
+def select_band(A, lo=None, hi=None, complement=False, transposed=None, stream=None):
+    """the stored entries (i, j) of A with lo <= j - i <= hi (None: unbounded on that side; complement: the entries outside the band) as a
+    new matrix (bmsp_matrix_select_band), its tiles in layout `transposed` (None: A's layout); returns (matrix, {"nnz_in", "nnz_out",
+    "blocks_in", "blocks_out"}).  No value is read; lo > hi is the empty band."""
+    lo, hi = _band_bounds(lo, hi)
+    lay = A.info()["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    st = SelectStats()
+    check(lib().bmsp_matrix_select_band(A.h, lo, hi, SELECT_COMPLEMENT if complement else 0, lay, stream, C.byref(h), C.byref(st)))
+    return BmSpMatrix(h.value), st.as_dict()
+
+
+def band_count(A, lo=None, hi=None, complement=False, stream=None):
+    """the stats select_band() would return, without making the output (the mark pass and the scan only)."""
+    lo, hi = _band_bounds(lo, hi)
+    st = SelectStats()
+    check(lib().bmsp_matrix_select_band(A.h, lo, hi, SELECT_COMPLEMENT if complement else 0, 0, stream, None, C.byref(st)))
+    return st.as_dict()
+
+
+def tril(A, k=0, transposed=None, stream=None):
+    """the stored entries of A with col - row <= k as a new matrix (numpy's tril on the stored pattern): select_band(A, None, k)"""
+    return select_band(A, None, k, False, transposed, stream)[0]
+
+
+def triu(A, k=0, transposed=None, stream=None):
+    """the stored entries of A with col - row >= k as a new matrix (numpy's triu on the stored pattern): select_band(A, k, None)"""
+    return select_band(A, k, None, False, transposed, stream)[0]
+
+
+def offdiagonal(A, transposed=None, stream=None):
+    """the stored entries of A with row != col as a new matrix (the off-diagonal part of a splitting): the complement of band(0, 0)"""
+    return select_band(A, 0, 0, True, transposed, stream)[0]
+
+
+def select_mask(A, M, complement=False, transposed=None, stream=None):
+    """the stored entries of A at the coordinates M stores (complement: does not store) as a new matrix (bmsp_matrix_select_mask), its
+    tiles in layout `transposed` (None: A's layout); returns (matrix, stats dict as select_band).  M has A's shape, any dtype and either
+    layout; its values are never read."""
+    lay = A.info()["transposed"] if transposed is None else int(bool(transposed))
+    h = C.c_void_p()
+    st = SelectStats()
+    check(lib().bmsp_matrix_select_mask(A.h, M.h, SELECT_COMPLEMENT if complement else 0, lay, stream, C.byref(h), C.byref(st)))
+    return BmSpMatrix(h.value), st.as_dict()
+
+
+def mask_count(A, M, complement=False, stream=None):
+    """the stats select_mask() would return, without making the output."""
+    st = SelectStats()
+    check(lib().bmsp_matrix_select_mask(A.h, M.h, SELECT_COMPLEMENT if complement else 0, 0, stream, None, C.byref(st)))
+    return st.as_dict()
 
 
 def diagonal(A, stream=None):
@@ -1335,36 +1415,12 @@ def fsai_values(A, G, op="N", scale="sqrt", pivot=False, stream=None):
     return (G, info.as_dict(), d) if pivot else (G, info.as_dict())
 
 
-class _TorchView:
-    """a DeviceArray seen through __cuda_array_interface__ (no copy)"""
-
-    def __init__(self, d):
-        self.keep = d
-        self.__cuda_array_interface__ = {"shape": (d.n,), "typestr": d.dtype.str, "data": (d.ptr, False), "version": 2}
-
-
 def fsai_pattern(A, theta=0.0, transposed=None, stream=None):
     """A pattern for fsai(): the lower triangle of A's pattern, after prune(theta, "row_rel", keep_diagonal=True) when theta > 0 (tiles in
-    layout `transposed`; None: A's layout).  Set-up convenience, not hot path: the entries take the COO route on the device and a torch
-    mask (torch must be importable, and imported before this module)."""
-    import torch
-    i = A.info()
+    layout `transposed`; None: A's layout).  Both steps run on the device (bmsp_matrix_prune, bmsp_matrix_select_band)."""
+    lay = A.info()["transposed"] if transposed is None else int(bool(transposed))
     M = prune(A, float(theta), "row_rel", True, None, stream)[0] if theta > 0 else A
-    lay = i["transposed"] if transposed is None else int(bool(transposed))
-    h = C.c_void_p()
-    if M.nnz == 0:
-        check(lib().bmsp_matrix_from_coo_device(i["num_rows"], i["num_cols"], 0, None, None, None, lay, i["dtype"], stream, C.byref(h)))
-        return BmSpMatrix(h.value)
-    r, c, v = M.to_coo_device(stream)
-    synchronize()
-    tr, tc, tv = (torch.as_tensor(_TorchView(d), device="cuda") for d in (r, c, v))
-    keep = tc <= tr
-    kr, kc, kv = tr[keep].contiguous(), tc[keep].contiguous(), tv[keep].contiguous()
-    torch.cuda.synchronize()
-    check(lib().bmsp_matrix_from_coo_device(i["num_rows"], i["num_cols"], int(kr.numel()), kr.data_ptr(), kc.data_ptr(), kv.data_ptr(), lay,
-                                            i["dtype"], stream, C.byref(h)))
-    synchronize()
-    return BmSpMatrix(h.value)
+    return tril(M, 0, lay, stream)
 
 
 class Fsai:

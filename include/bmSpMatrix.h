@@ -248,6 +248,30 @@ public:
         return out;
     }
 
+    /* the stored entries with lo <= col - row <= hi (complement: the others) as a new matrix (bmsp_matrix_select_band); BMSP_BAND_MIN /
+     * BMSP_BAND_MAX leave a side unbounded.  tril(k) = band(MIN, k), triu(k) = band(k, MAX); no value is read */
+    bmSpMatrix<valueType> band(int64_t lo, int64_t hi, bool complement = false, bool transposed_layout = false) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_select_band(h_, lo, hi, complement ? BMSP_SELECT_COMPLEMENT : 0, transposed_layout ? 1 : 0, nullptr, &t, nullptr));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+    bmSpMatrix<valueType> tril(int64_t k = 0, bool transposed_layout = false) const { return band(BMSP_BAND_MIN, k, false, transposed_layout); }
+    bmSpMatrix<valueType> triu(int64_t k = 0, bool transposed_layout = false) const { return band(k, BMSP_BAND_MAX, false, transposed_layout); }
+    /* the stored entries at the coordinates M stores (complement: does not store) as a new matrix (bmsp_matrix_select_mask); M has this
+     * matrix's shape, any value type and either layout, its values are never read */
+    template <class maskType>
+    bmSpMatrix<valueType> mask(const bmSpMatrix<maskType> &M, bool complement = false, bool transposed_layout = false) const
+    {
+        bmsp_matrix_t t = nullptr;
+        bmsp::check(bmsp_matrix_select_mask(h_, M.handle(), complement ? BMSP_SELECT_COMPLEMENT : 0, transposed_layout ? 1 : 0, nullptr, &t, nullptr));
+        bmSpMatrix<valueType> out;
+        out.reset(t);
+        return out;
+    }
+
     /* the diagonal as a device vector of min(num_rows, num_cols) entries, +0 where (i, i) is not stored (bmsp_matrix_diagonal) */
     bmsp::device_vector<typename bmsp::vector_of<valueType>::type> diagonal() const
     {
@@ -645,6 +669,26 @@ inline void bmSparse_prune(bmSpMatrix<valueType> &A, bmSpMatrix<valueType> &C, d
 {
     bmsp_matrix_t c = nullptr;
     bmsp::check(bmsp_matrix_prune(A.handle(), rule, tol, keep_diagonal ? BMSP_PRUNE_KEEP_DIAGONAL : 0, transposed_layout ? 1 : 0, nullptr, &c, stats));
+    C.reset(c);
+}
+
+/* C = the stored entries of A with lo <= col - row <= hi (bmsp_matrix_select_band) / at the coordinates M stores (bmsp_matrix_select_mask),
+ * or with `complement` the others; C's tiles column-major when transposed_layout; stats (optional) receives the entry and tile counts
+ * before and after. */
+template <class valueType>
+inline void bmSparse_select_band(bmSpMatrix<valueType> &A, bmSpMatrix<valueType> &C, int64_t lo, int64_t hi, bool complement = false,
+                                 bool transposed_layout = false, bmsp_select_stats *stats = nullptr)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_matrix_select_band(A.handle(), lo, hi, complement ? BMSP_SELECT_COMPLEMENT : 0, transposed_layout ? 1 : 0, nullptr, &c, stats));
+    C.reset(c);
+}
+template <class valueType, class maskType>
+inline void bmSparse_select_mask(bmSpMatrix<valueType> &A, bmSpMatrix<maskType> &M, bmSpMatrix<valueType> &C, bool complement = false,
+                                 bool transposed_layout = false, bmsp_select_stats *stats = nullptr)
+{
+    bmsp_matrix_t c = nullptr;
+    bmsp::check(bmsp_matrix_select_mask(A.handle(), M.handle(), complement ? BMSP_SELECT_COMPLEMENT : 0, transposed_layout ? 1 : 0, nullptr, &c, stats));
     C.reset(c);
 }
 

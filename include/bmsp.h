@@ -190,6 +190,32 @@ typedef struct { int64_t nnz_in, nnz_out, blocks_in, blocks_out; } bmsp_prune_st
 int bmsp_matrix_prune(bmsp_matrix_t A, int rule, double tol, int flags, int out_transposed, void *stream, bmsp_matrix_t *out,
                       bmsp_prune_stats *stats);
 int bmsp_matrix_row_absmax(bmsp_matrix_t A, void *d_rowmax, void *stream);
+/* Selection: out = the stored entries of A a POSITION predicate keeps, on the device (no COO round trip).  Pruning shrinks a matrix by
+ * value; this shrinks it by coordinate: the triangle the solves, ILU(0) and FSAI are specified on, the band of a preconditioner, the
+ * off-diagonal part of a splitting, A restricted to another matrix's pattern (a Galerkin product kept on A's pattern) or to its
+ * complement (the fill-in of a product, A*A without spy(A)).  No predicate reads a value.
+ *   bmsp_matrix_select_band keeps a stored entry (i, j) iff lo <= j - i <= hi, in matrix coordinates whatever the tile layout.  Every
+ *       pair of int64 values is legal: lo > hi is the empty band, BMSP_BAND_MIN / BMSP_BAND_MAX mean unbounded (both bounds are clamped
+ *       to +-2^36; coordinates are below 2^35).  tril(A, k) = band(MIN, k), triu(A, k) = band(k, MAX), the diagonal part = band(0, 0),
+ *       the off-diagonal part = band(0, 0) with BMSP_SELECT_COMPLEMENT.
+ *   bmsp_matrix_select_mask keeps a stored entry of A iff M stores the same coordinate.  M has A's shape, any dtype and either layout;
+ *       its values are never read (a stored zero of M counts as stored); M may be A; its block-row pointer is built if missing.
+ *   BMSP_SELECT_COMPLEMENT in `flags` keeps exactly the entries the predicate rejects.
+ *   Output, count-only calls, stream and side effects are bmsp_matrix_prune's: a fresh pool-owned handle of A's shape and dtype, tiles in
+ *       layout `out_transposed`, whose four arrays and block-row pointer equal, bit for bit, what the builders make from the COO of the
+ *       kept entries in that layout (values move as raw bits, emptied tiles disappear, 0 tiles is a valid matrix, offsets hold
+ *       block_num+1 entries); out == NULL with stats != NULL counts only; A, M and their caches are never modified; the call runs on
+ *       `stream` and synchronises it before it returns.  Tiles keep their keys and their order: nothing is sorted or re-tiled.
+ *   Refused with BMSP_ERR_INVALID, the message naming the argument, scalars before handles: flags with unknown bits; out_transposed not
+ *   0 / 1; out and stats both NULL; null A or M; shapes that differ; row-panel views.  BMSP_ERR_LIMIT: as for bmsp_matrix_prune, on A. */
+#define BMSP_SELECT_COMPLEMENT 1            /* flags bit 0: keep what the predicate rejects */
+#define BMSP_BAND_MIN INT64_MIN             /* lo: unbounded below */
+#define BMSP_BAND_MAX INT64_MAX             /* hi: unbounded above */
+typedef bmsp_prune_stats bmsp_select_stats; /* nnz_in, nnz_out, blocks_in, blocks_out */
+int bmsp_matrix_select_band(bmsp_matrix_t A, int64_t lo, int64_t hi, int flags, int out_transposed, void *stream,
+                            bmsp_matrix_t *out, bmsp_select_stats *stats);
+int bmsp_matrix_select_mask(bmsp_matrix_t A, bmsp_matrix_t M, int flags, int out_transposed, void *stream,
+                            bmsp_matrix_t *out, bmsp_select_stats *stats);
 /* Diagonal operations: what connects a device VECTOR to a matrix besides bmsp_spmv, on the device (no COO round trip).  Nothing in the
  * reference is replaced: it has no diagonal, scaling or addition entry point (include/bmSpMatrix.h:20-40 declares the builders,
  * generate_coo and compare only).  Vectors are float for F32 / F16 matrices and double for F64 (the convention of bmsp_spmv's u and of
